@@ -18,6 +18,10 @@ timed region (crocoddyl_amd/dist.py). Under torchrun the ranks come from its
 environment; `python bench.py --gpus N` without one starts the N ranks itself
 (launch_ranks) and relays rank 0's line.
 
+A plain run sets up, warms up, times the --steps steps and prints the line; what takes
+runs of its own (the CPU baseline, the other protocol, boxfddp's FDDP backward) is behind
+--full. --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
+
 Prints one JSON line (rank 0).
 """
 import argparse
@@ -393,6 +397,33 @@ def trials_summary(trials):
             "hist": np.bincount(trials.astype(int), minlength=11)[1:].tolist()}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: all files of one dump together
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write the job's outputs, {name: tensor with one row per batch
+    element}, as out_dir/<name>.npy (float64). Where they exceed `limit` bytes in all,
+    the same seeded sample of the batch elements is kept of every array (ascending;
+    the sample depends only on the batch size and the row sizes), and the kept elements'
+    indices are written as out_dir/elements.npy (float64 as well)."""
+    os.makedirs(out_dir, exist_ok=True)
+    nrow = next(iter(arrays.values())).shape[0]
+    row_bytes = 8 + sum(8 * int(np.prod(a.shape[1:])) for a in arrays.values())  # + the element's index
+    keep = min(nrow, (limit - 1024 * (len(arrays) + 1)) // row_bytes)  # 1 KiB per file for the .npy header
+    sel = np.arange(nrow)
+    if keep < nrow:
+        sel = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(nrow, size=keep, replace=False))
+    written = 0
+    for name, a in dict(arrays, elements=sel).items():
+        if name != "elements":
+            a = a.detach().cpu().numpy()[sel]
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, np.ascontiguousarray(a, dtype=np.float64))
+        written += os.path.getsize(path)
+    assert written <= limit, (written, limit)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -487,7 +518,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C5_talos_walk")
     ap.add_argument("--batch", type=int, default=None, help="elements per GPU (default: the config's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--solver", choices=["fddp", "boxfddp"], default="fddp",
                     help="boxfddp: SolverBoxFDDP with control limits (C5: the code-built Talos effortLimit on the "
                          "actuated joints, parity unpinned; elsewhere |u| <= 1); default protocol 'feasible': an untimed "
@@ -498,12 +529,23 @@ def main():
                          "start every step (bipedal_walk_optctrl.py:36-43); shift: receding horizon, gait knots "
                          "rotated (circularAppend) + device shift of x0/xs/us, then the warm-started solve")
     ap.add_argument("--secondary-steps", type=int, default=5,
-                    help="steps of the other protocol, reported beside the headline (1 GPU only; 0: off)")
+                    help="with --full: steps of the other protocol, reported beside the headline (1 GPU only; 0: off)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also measure what takes runs of its own: the CPU baseline (unless "
+                         "--no-cpu-baseline), the other protocol (--secondary-steps) and, with --solver boxfddp, the "
+                         "FDDP backward on the same step. Off by default: a plain run sets up, warms up, times the "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the gathered xs, us and "
+                         "per-element results, float64) as DIR/<name>.npy, at most 64 MB in all: of a larger output "
+                         "a fixed, seeded sample of the batch elements (their indices in DIR/elements.npy)")
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rehearsal", action="store_true",
                     help="allow more ranks than GPUs (ranks share devices, gloo collectives): a rehearsal of the "
                          "N-GPU job, marked as such in the JSON line, n_gpus = the distinct devices used")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     box = args.solver == "boxfddp"
     if args.protocol is None:
         args.protocol = "feasible" if box else "fixed"
@@ -585,6 +627,8 @@ def main():
     rank_elapsed = elapsed
     elapsed, total_iters = cdist.job_time_and_work(elapsed, iters, f"cuda:{dev}")
     assert xs_all.shape[0] == us_all.shape[0] == res_all.shape[0] == ws * B
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"xs": xs_all, "us": us_all, "results": res_all})
     # per-rank diagnostics (outside the timed region): the timed loop's own time, the
     # gather's time and bytes, the rank's iterations; max/min imbalance per column
     names = ["elapsed_s", "solve_s", "gather_s", "iterations", "mean_trials_last_step", "device", "world_size"]
@@ -603,7 +647,7 @@ def main():
                       "rank's GPU; world_size: dist.get_world_size() seen by the rank")
 
     box_bwd = None
-    if box and ws == 1 and args.protocol == "feasible":
+    if args.full and box and ws == 1 and args.protocol == "feasible":
         # the FDDP backward on the same step: SolverFDDP on the same problems, restarted
         # from the same feasible iterate (FDDP gains: no box QP)
         sf = make_shard_solver(args.config, B, rank, dev, False, presolve=False)
@@ -627,7 +671,7 @@ def main():
         del sf, fr
 
     secondary = None
-    if ws == 1 and args.secondary_steps > 0 and args.protocol != "feasible":
+    if args.full and ws == 1 and args.secondary_steps > 0 and args.protocol != "feasible":
         other = "shift" if args.protocol == "fixed" else "fixed"
         del xs_all, us_all, res_all
         s2, step2 = make_stepper(other)
@@ -718,7 +762,7 @@ def main():
         dominant = max(rooflines, key=lambda k: rooflines[k][0])
         roof = dict(rooflines[dominant][1], dominant_of=sorted(rooflines), pmc=pmc_prov)
         cpu = None
-        if ws == 1 and not args.no_cpu_baseline:
+        if args.full and ws == 1 and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline(args.config, T, synthetic.seed_of(args.config), args.protocol, box=box)
             except Exception as e:  # reported, never fatal for the GPU number

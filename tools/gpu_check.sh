@@ -21,6 +21,6 @@ if [ -n "$DIST" ]; then
   timeout -k 10 400 python -u bench.py --gpus 2 --rehearsal --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_gpus2.json 2> $O/bench_gpus2.err || { tail -20 $O/bench_gpus2.err; exit 1; }
 fi
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 400 python -u bench.py --steps 10 --warmup 2 --no-cpu-baseline ${BENCH_ARGS} > $O/bench_c5.json 2> $O/bench_c5.err || { tail -5 $O/bench_c5.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 2 --no-cpu-baseline ${BENCH_ARGS} > $O/bench_c5.json 2> $O/bench_c5.err || { tail -5 $O/bench_c5.err; exit 1; }
   python -c "import json;d=json.load(open('$O/bench_c5.json'));print(d['value'],d['kernel_ms_per_step'],d['secondary_protocol'] and d['secondary_protocol']['value'])"
 fi

@@ -16,5 +16,5 @@ timeout -s KILL 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fet
 timeout -s KILL 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o run -- python3 bench.py $PARGS > $O/pmc_write.log 2>&1 || { tail -5 $O/pmc_write.log; exit 1; }
 timeout -s KILL 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma -o run -- python3 bench.py $PARGS > $O/pmc_mfma.log 2>&1 || { tail -5 $O/pmc_mfma.log; exit 1; }
 find $O -name "*.csv" | head -20
-# the bench line with its CPU baseline (the default command), kept beside the profile
-timeout -k 10 600 python3 bench.py ${BENCH_ARGS} > $O/bench_with_cpu.json 2> $O/bench_with_cpu.log || { tail -5 $O/bench_with_cpu.log; exit 1; }
+# the bench line with its CPU baseline (bench.py --full), kept beside the profile
+timeout -k 10 600 python3 bench.py --full ${BENCH_ARGS} > $O/bench_with_cpu.json 2> $O/bench_with_cpu.log || { tail -5 $O/bench_with_cpu.log; exit 1; }
