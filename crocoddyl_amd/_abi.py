@@ -27,6 +27,10 @@ Q_QUU_INV = 18
 
 SOLVER_FDDP, SOLVER_BOXFDDP = 0, 1
 
+# fddp_get_kernel_info: the kernel variants (csrc/ktab.hpp)
+MB_W2, MB_W1, MB_X2, MB_X8, MB_S2 = range(5)
+FWD_GENERIC, FWD_FAST, FWD_MB, FWD_MB2 = range(4)
+
 
 class Dims(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ndx", C.c_int32), ("nu_max", C.c_int32), ("T", C.c_int32), ("B", C.c_int32)]
@@ -129,6 +133,7 @@ PROTOS_GPU = {
     "get_solver_kind": (C.c_int, [P, I32]),
     "set_callback": (C.c_int, [P, IterationCallback, C.c_void_p]),
     "get_line_search_info": (C.c_int, [P, I32, I32]),
+    "get_kernel_info": (C.c_int, [P, I32]),
     "boxqp_default_params": (None, [C.POINTER(BoxQPParams)]),
     "boxqp_solve": (C.c_int, [C.c_int, C.c_int, C.c_int, D, D, D, D, D, C.POINTER(BoxQPParams), D, U64, U64, D, I32]),
 }

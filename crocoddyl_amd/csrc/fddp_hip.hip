@@ -347,6 +347,12 @@ struct fddp_handle_s {
   bool npar_chosen = false;  // choose_npar has set D.npar
   double ls_slots = 0.;     // rollout workgroups resident on the device at once
   int fwd_mb_variant = -1;  // rollout_variant's choice (-1: not yet made; reset by apply_knots)
+  // variant overrides read from the environment by apply_knots (unset: the rules decide)
+  int env_mb_w1 = -1;           // FDDP_MB_W1: 0 / 1 forces the 2- / 1-wave/EU calcDiff build
+  int env_mb_nt = 0;            // FDDP_MB_NT: 128 / 256 / 512 forces the calcDiff workgroup size
+  int env_mb_spill = -1;        // FDDP_MB_SPILL: 0 forces the all-LDS calcDiff plan
+  bool env_fwd_mb_off = false;  // FDDP_FWD_MB=0: the generic rollout on multibody horizons
+  int env_fwd_mbw = 0;          // FDDP_FWD_MBW: 2 / 3 forces the rollout's waves/EU build
   hipStream_t stream = nullptr;
   std::vector<fddp_knot_desc> knots;
   int64_t n_params = 0;
@@ -482,35 +488,24 @@ int launch_fused(fddp_handle* h, int sel_calc, int sel_diff, int gaps) {
 // The knot-parallel kernel's LDS plan leaves room for one workgroup per CU: take the
 // 1-wave/EU build (no spills; FDDP_MB_W1=0 forces the 2-wave one, for A/B runs).
 static bool mb_one_per_cu(const fddp_handle* h) {
-  static const int env = [] {
-    const char* e = std::getenv("FDDP_MB_W1");
-    return e ? (e[0] == '0' ? 0 : 1) : -1;
-  }();
-  return env >= 0 ? env == 1 : h->mb_diff_smem > 80 * 1024;
+  return h->env_mb_w1 >= 0 ? h->env_mb_w1 == 1 : h->mb_diff_smem > 80 * 1024;
 }
 // 512-thread (8-wave) workgroups for the one-per-CU plans: two waves per SIMD where the
 // 256-thread plan has one (C5 calcDiff 66 -> 59 ms); FDDP_MB_NT=256 / 512 forces
-static bool mb_x8(const fddp_handle* h) {
-  static const int env = [] {
-    const char* e = std::getenv("FDDP_MB_NT");
-    return e ? std::atoi(e) : 0;
-  }();
-  return env ? env == 512 : mb_one_per_cu(h);
-}
+static bool mb_x8(const fddp_handle* h) { return h->env_mb_nt ? h->env_mb_nt == 512 : mb_one_per_cu(h); }
 // 128-thread (2-wave) workgroups for the small trees whose LDS plan fits four per CU
 static bool mb_x2(const fddp_handle* h) {
-  static const int env = [] {
-    const char* e = std::getenv("FDDP_MB_NT");
-    return e ? std::atoi(e) : 0;
-  }();
-  return env ? env == 128 : (h->mb_nj <= 16 && h->mb_diff_smem <= 40 * 1024);
+  return h->env_mb_nt ? h->env_mb_nt == 128 : (h->mb_nj <= 16 && h->mb_diff_smem <= 40 * 1024);
+}
+// The knot-parallel kernel's variant (ktab::MB_*) for the handle's LDS plan
+static int mb_variant(const fddp_handle* h) {
+  return h->D.mbspill ? ktab::MB_S2
+                      : mb_x2(h) ? ktab::MB_X2 : (mb_x8(h) ? ktab::MB_X8 : (mb_one_per_cu(h) ? ktab::MB_W1 : ktab::MB_W2));
 }
 // Multibody knots (knot-parallel): calc for sel_calc, calcDiff for sel_diff (-1: none).
 int launch_mb(fddp_handle* h, int sel_calc, int sel_diff) {
   const Dev& D = h->D;
-  const int v = D.mbspill ? ktab::MB_S2
-                           : mb_x2(h) ? ktab::MB_X2 : (mb_x8(h) ? ktab::MB_X8 : (mb_one_per_cu(h) ? ktab::MB_W1 : ktab::MB_W2));
-  KLAUNCH(ktab::mb_knot(v, dim3(D.T + 1, D.B), h->mb_diff_smem, h->stream, D, sel_calc, sel_diff));
+  KLAUNCH(ktab::mb_knot(mb_variant(h), dim3(D.T + 1, D.B), h->mb_diff_smem, h->stream, D, sel_calc, sel_diff));
   return FDDP_OK;
 }
 int launch_calc(fddp_handle* h, int sel) {
@@ -595,13 +590,7 @@ static int ensure_par_slots(fddp_handle* h) {
 
 // every knot multibody: the rollout variant with only the multibody calc compiled in
 // (FDDP_FWD_MB=0 selects the generic one, for A/B runs)
-static bool mb_rollout(const fddp_handle* h) {
-  static const bool off = [] {
-    const char* e = std::getenv("FDDP_FWD_MB");
-    return e && e[0] == '0';
-  }();
-  return h->all_mb && !off;
-}
+static bool mb_rollout(const fddp_handle* h) { return h->all_mb && !h->env_fwd_mb_off; }
 
 // Workgroups of `fn` one CU holds at once with `smem` bytes of dynamic LDS: the occupancy
 // API's answer, capped by the LDS allocated in 2 KB granules (measured on gfx950,
@@ -622,10 +611,7 @@ static int resident_per_cu(const void* fn, size_t smem) {
 static int rollout_variant(fddp_handle* h) {
   if (!mb_rollout(h)) return ktab::FWD_GENERIC;
   if (h->fwd_mb_variant >= 0) return h->fwd_mb_variant;
-  static const int env = [] {
-    const char* e = std::getenv("FDDP_FWD_MBW");
-    return e ? std::atoi(e) : 0;
-  }();
+  const int env = h->env_fwd_mbw;
   int dev_cus = 0;
   (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, h->device);
   const bool three = resident_per_cu(ktab::forward_fn(ktab::FWD_MB), h->fwd_smem) >= 3;
@@ -855,6 +841,19 @@ int apply_knots(fddp_handle* h, const fddp_knot_desc* knots, const double* param
   const int64_t K1 = (int64_t)d.T + 1;
   int rc;
   h->knots.assign(knots, knots + K1);
+  {  // the variant overrides (A/B runs, the variant tests), per handle like FDDP_FAST below
+    auto env_int = [](const char* name, int unset) {
+      const char* e = std::getenv(name);
+      return e ? std::atoi(e) : unset;
+    };
+    const char* w1 = std::getenv("FDDP_MB_W1");
+    h->env_mb_w1 = w1 ? (w1[0] == '0' ? 0 : 1) : -1;
+    h->env_mb_nt = env_int("FDDP_MB_NT", 0);
+    h->env_mb_spill = env_int("FDDP_MB_SPILL", -1);
+    const char* fm = std::getenv("FDDP_FWD_MB");
+    h->env_fwd_mb_off = fm && fm[0] == '0';
+    h->env_fwd_mbw = env_int("FDDP_FWD_MBW", 0);
+  }
   {
     int64_t pmax = 0;
     int mb_nj = 0, mb_njac = 0, mb_nc = 0;
@@ -923,10 +922,7 @@ int apply_knots(fddp_handle* h, const fddp_knot_desc* knots, const double* param
     // the calcDiff's LDS plan: spilled to the output blocks where the all-LDS plan would
     // leave room for one workgroup per CU only (multibody.hpp diff_spill; FDDP_MB_SPILL=0
     // forces the all-LDS plan, for A/B runs)
-    static const int spill_env = [] {
-      const char* e = std::getenv("FDDP_MB_SPILL");
-      return e ? std::atoi(e) : -1;
-    }();
+    const int spill_env = h->env_mb_spill;
     auto plan_doubles = [&](int spill) {  // the largest knot's plan under spill flags `spill`
       int64_t mx = 0;
       for (const MbShape& q : shapes)
@@ -1486,6 +1482,20 @@ int fddp_solve(fddp_handle* h, int maxiter, int is_feasible, double reg_init, fd
     fprintf(stderr, "fddp box stats: %llu QPs, %.3f Newton iterations and %.3f inverses per QP\n", bs[0],
             bs[0] ? (double)bs[1] / bs[0] : 0., bs[0] ? (double)bs[2] / bs[0] : 0.);
   }
+  return FDDP_OK;
+}
+
+int fddp_get_kernel_info(fddp_handle* h, int32_t out[8]) {
+  if (!h || !out) return fail(FDDP_ERR_INVALID_ARG, "fddp_get_kernel_info: null argument");
+  DeviceGuard g(h->device);
+  out[0] = h->has_mb && !h->fast ? mb_variant(h) : -1;
+  out[1] = h->fast ? (int)ktab::FWD_FAST : rollout_variant(h);
+  out[2] = h->bwd_variant;
+  out[3] = h->D.mbspill;
+  out[4] = (int32_t)h->mb_diff_smem;
+  out[5] = (int32_t)(h->fast ? h->fwd_fast_smem : h->fwd_smem);
+  out[6] = h->D.npar;
+  out[7] = 0;
   return FDDP_OK;
 }
 

@@ -270,6 +270,18 @@ int fddp_set_callback(fddp_handle* h, fddp_iteration_callback cb, void* user);
  * the number of rollout dispatches it made. */
 int fddp_get_line_search_info(fddp_handle* h, int* group_size, int* launches);
 
+/* Diagnostics of the kernel dispatch the handle's knots and the environment overrides
+ * (FDDP_MB_W1 / FDDP_MB_NT / FDDP_MB_SPILL / FDDP_FWD_MB / FDDP_FWD_MBW / FDDP_FAST /
+ * FDDP_BACKWARD / FDDP_BWD_WAVES, read when the knots are applied: fddp_create,
+ * fddp_set_knots) select; read-only. out[0] the multibody calcDiff variant (0 256 threads
+ * at 2 waves/EU, 1 the same at 1 wave/EU, 2 128 threads, 3 512 threads, 4 the spilled
+ * plan; -1 no multibody knots), out[1] the rollout (0 generic, 1 dense-knot fast path, 2 /
+ * 3 multibody-only at three / two workgroups per CU), out[2] the Riccati sweep (0 generic,
+ * else (NTL*10+MTL)*10+waves of the MFMA sweep), out[3] the calcDiff plan's spill flags,
+ * out[4] / out[5] the dynamic LDS bytes of the multibody calcDiff / the rollout, out[6]
+ * the line search's trial-group size, out[7] reserved (0). */
+int fddp_get_kernel_info(fddp_handle* h, int32_t out[8]);
+
 /* Results of the last solve / current solver state per element. */
 int fddp_get_results(fddp_handle* h, fddp_result* out);
 /* xs: B*(T+1)*nx, us: B*T*nu_max. on_device != 0: `out` is a device pointer

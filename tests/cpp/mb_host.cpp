@@ -30,23 +30,59 @@ double mb_host_calc(const double* P, int nx, const double* x, const double* u, i
   return knot_calc_x(HostExec{256}, P, nx, x, u, use_u != 0, xnext, w.data());
 }
 
-void mb_host_calc_diff(const double* P, int nx, int m, const double* x, const double* u, int use_u, double* Fx,
-                       double* Fu, double* Lxx, double* Lxu, double* Luu, double* Lx, double* Lu, double* xnext,
-                       double* cost) {
+// calcDiff of a block under plan flags `spill` (< 0: the block's own, diff_spill;
+// MB_HOST_SPILL=0 forces the all-LDS plan then)
+static void calc_diff_under(int spill, const double* P, int nx, int m, const double* x, const double* u, int use_u,
+                            double* Fx, double* Fu, double* Lxx, double* Lxu, double* Luu, double* Lx, double* Lu,
+                            double* xnext, double* cost) {
   const Blk b = parse(P);
   bool vc = false;
   const int njac = count_jac_costs(b, &vc);
   const int nu = b.nj - b.nun, nrows = count_cost_rows(b, nu);
-  // the device's plan for this block (spilled to the output blocks on the large trees);
-  // MB_HOST_SPILL=0 forces the all-LDS plan
-  const char* sp = std::getenv("MB_HOST_SPILL");
-  const int spill = sp && sp[0] == '0' ? 0 : diff_spill(b.nj, njac, b.nc, vc, nu, nrows, (int64_t)P[3], m);
+  if (spill < 0) {
+    const char* sp = std::getenv("MB_HOST_SPILL");
+    spill = sp && sp[0] == '0' ? 0 : diff_spill(b.nj, njac, b.nc, vc, nu, nrows, (int64_t)P[3], m);
+  }
   std::vector<double> w(diff_layout(b.nj, njac, b.nc, vc, nu, nrows, spill).htotal, 0.);
   // MB_HOST_NT: the workgroup size the lanes emulate (128 / 256 / 512: the device's
   // small-tree, default and 8-wave calcDiff kernels)
   const char* e = std::getenv("MB_HOST_NT");
   knot_calc_diff_x(HostExec{e ? std::atoi(e) : kMbDiffNT}, P, nx, m, x, u, use_u != 0, w.data(), Fx, Fu, Lxx, Lxu, Luu,
                    Lx, Lu, xnext, cost, nullptr, spill);
+}
+
+void mb_host_calc_diff(const double* P, int nx, int m, const double* x, const double* u, int use_u, double* Fx,
+                       double* Fu, double* Lxx, double* Lxu, double* Luu, double* Lx, double* Lu, double* xnext,
+                       double* cost) {
+  // the device's plan for this block (spilled to the output blocks on the large trees)
+  calc_diff_under(-1, P, nx, m, x, u, use_u, Fx, Fu, Lxx, Lxu, Luu, Lx, Lu, xnext, cost);
+}
+
+// The same under caller-supplied plan flags: a handle takes its flags from the maxima over
+// all its knots (fddp_hip.hip apply_knots), so a knot can run a plan its own shape would
+// not pick (a flight knot under the flags of the contact knots beside it).
+void mb_host_calc_diff_flags(const double* P, int nx, int m, int spill, const double* x, const double* u, int use_u,
+                             double* Fx, double* Fu, double* Lxx, double* Lxu, double* Luu, double* Lx, double* Lu,
+                             double* xnext, double* cost) {
+  calc_diff_under(spill, P, nx, m, x, u, use_u, Fx, Fu, Lxx, Lxu, Luu, Lx, Lu, xnext, cost);
+}
+
+// The block's shape as the dispatch reads it (nj, njac, nc, vcols, nu, nrows, block
+// doubles) and the LDS bytes of its calcDiff plan under flags `spill` with a parameter
+// area of `psz` doubles (the handle's largest block).
+int64_t mb_host_plan_under(const double* P, int spill, int64_t psz, int64_t* shape) {
+  const Blk b = parse(P);
+  bool vc = false;
+  const int njac = count_jac_costs(b, &vc);
+  const int nu = b.nj - b.nun, nrows = count_cost_rows(b, nu);
+  const int64_t f[] = {b.nj, njac, b.nc, vc ? 1 : 0, nu, nrows, (int64_t)P[3]};
+  for (int i = 0; i < 7; ++i) shape[i] = f[i];
+  return 8 * (fddp::pad2(diff_layout(b.nj, njac, b.nc, vc, nu, nrows, spill).total) + fddp::pad2(psz));
+}
+
+// diff_spill of a shape (the handle's: the maxima over its knots)
+int mb_host_spill_flags(int nj, int njac, int nc, int vcols, int nu, int nrows, int64_t psz, int m) {
+  return diff_spill(nj, njac, nc, vcols != 0, nu, nrows, psz, m);
 }
 }
 

@@ -158,6 +158,51 @@ class Gpu:
     def quu_inv(self):
         return self.quantity(_abi.Q_QUU_INV, self.dims.T, self.dims.nu_max * self.dims.nu_max)
 
+    def kernel_info(self):
+        """fddp_get_kernel_info: the kernel variants this handle launches, by name."""
+        a = np.zeros(8, dtype=np.int32)
+        self._ok(self.L.fddp_get_kernel_info(self.h, a.ctypes.data_as(_abi.I32)))
+        return dict(zip(("mb", "fwd", "bwd", "mbspill", "mb_diff_smem", "fwd_smem", "npar"), (int(v) for v in a)))
+
+
+def start(name, S):
+    """The candidate the phase tests start from: the reference benchmark's warm start on
+    the C5 walk, seeded uniform states / controls otherwise."""
+    d = S["dims"]
+    if name.startswith("C5"):
+        import bench
+        return bench.warm_start_arrays(name, S["running"], S["x0s"], d)
+    rng = np.random.default_rng(5)
+    return rng.uniform(-1, 1, (d.B, d.T + 1, d.nx)), rng.uniform(-1, 1, (d.B, d.T, d.nu_max))
+
+
+ALL_BLOCKS = ("Fx", "Fu", "Lxx", "Lxu", "Luu", "Lx", "Lu", "fs")
+
+
+def phases(h, xs, us, alphas, xreg, blocks=("Fx", "Fu", "Lxx", "Lx", "fs")):
+    """calcDiff, backwardPass, forwardPass(alpha) for each alpha, from a fresh solver state.
+    blocks: the calcDiff outputs read back (ALL_BLOCKS: every one)."""
+    d = h.dims
+    n, m = d.ndx, d.nu_max
+    h.set_candidate(xs, us, False)
+    h.set_solver_state(it=0, xreg=xreg, ureg=xreg)
+    out = {"cost": h.ddp_calc_diff()}
+    for name, q, per in (("Fx", _abi.Q_FX, n * n), ("Fu", _abi.Q_FU, n * m), ("Lxx", _abi.Q_LXX, n * n),
+                         ("Lxu", _abi.Q_LXU, n * m), ("Luu", _abi.Q_LUU, m * m), ("Lx", _abi.Q_LX, n),
+                         ("Lu", _abi.Q_LU, m), ("fs", _abi.Q_FS, n)):
+        if name in blocks:
+            out[name] = h.quantity(q, d.T + 1, per)
+    out["bwd_status"] = h.backward_pass()
+    for name, q, nk, per in (("K", _abi.Q_K, d.T, m * n), ("k", _abi.Q_KV, d.T, m), ("Vxx", _abi.Q_VXX, d.T + 1, n * n),
+                             ("Vx", _abi.Q_VX, d.T + 1, n), ("Qu", _abi.Q_QU, d.T, m), ("Quu", _abi.Q_QUU, d.T, m * m)):
+        out[name] = h.quantity(q, nk, per)
+    for a in alphas:
+        rc, ct, st = h.forward_pass(a)
+        assert rc == 0
+        out[f"cost_try@{a}"], out[f"fwd_status@{a}"] = ct, st
+        out[f"xs_try@{a}"], out[f"us_try@{a}"] = h.xs(trial=True), h.us(trial=True)
+    return out
+
 
 def rel_err(a, b):
     """One max-abs error over the whole array / max(1, max|b|). Coarse: small components

@@ -9,6 +9,7 @@ import pytest
 
 import helpers
 import oracle_lib
+from helpers import phases as _phases, start as _start
 from crocoddyl_amd import _abi
 
 pytestmark = pytest.mark.gpu
@@ -16,38 +17,6 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-8  # element-wise; 4x the oracle's own one-ulp spread where the knots are worse conditioned
 
 CASES = [("C5_talos_walk", dict(T=8, B=3)), ("C2_lqr", dict(T=100, B=8))]
-
-
-def _start(name, S):
-    d = S["dims"]
-    if name.startswith("C5"):
-        import bench
-        return bench.warm_start_arrays(name, S["running"], S["x0s"], d)
-    rng = np.random.default_rng(5)
-    return rng.uniform(-1, 1, (d.B, d.T + 1, d.nx)), rng.uniform(-1, 1, (d.B, d.T, d.nu_max))
-
-
-def _phases(h, xs, us, alphas, xreg):
-    """calcDiff, backwardPass, forwardPass(alpha) for each alpha, from a fresh solver state."""
-    d = h.dims
-    n, m = d.ndx, d.nu_max
-    h.set_candidate(xs, us, False)
-    h.set_solver_state(it=0, xreg=xreg, ureg=xreg)
-    out = {"cost": h.ddp_calc_diff()}
-    for name, q, nk, per in (("Fx", _abi.Q_FX, d.T + 1, n * n), ("Fu", _abi.Q_FU, d.T + 1, n * m),
-                             ("Lxx", _abi.Q_LXX, d.T + 1, n * n), ("Lx", _abi.Q_LX, d.T + 1, n),
-                             ("fs", _abi.Q_FS, d.T + 1, n)):
-        out[name] = h.quantity(q, nk, per)
-    out["bwd_status"] = h.backward_pass()
-    for name, q, nk, per in (("K", _abi.Q_K, d.T, m * n), ("k", _abi.Q_KV, d.T, m), ("Vxx", _abi.Q_VXX, d.T + 1, n * n),
-                             ("Vx", _abi.Q_VX, d.T + 1, n), ("Qu", _abi.Q_QU, d.T, m), ("Quu", _abi.Q_QUU, d.T, m * m)):
-        out[name] = h.quantity(q, nk, per)
-    for a in alphas:
-        rc, ct, st = h.forward_pass(a)
-        assert rc == 0
-        out[f"cost_try@{a}"], out[f"fwd_status@{a}"] = ct, st
-        out[f"xs_try@{a}"], out[f"us_try@{a}"] = h.xs(trial=True), h.us(trial=True)
-    return out
 
 
 @pytest.mark.parametrize("xreg", [float("nan"), 1e-9])
