@@ -1,11 +1,18 @@
 // Multibody knot kernels (fddp_kernels.hpp mb_knot_kernel*), one variant per object:
 // the Makefile compiles this file once per FDDP_TU_MB = ktab::MB_W2 .. MB_S2.
-#include "fddp_kernels.hpp"
-#include "ktab.hpp"
-
 #ifndef FDDP_TU_MB
 #error "k_mb.hip is compiled with -DFDDP_TU_MB=<variant>"
 #endif
+// the spilled-plan kernel (MB_S2: the large trees, two workgroups per CU) takes the shape
+// arguments of the calcDiff's matrix-core products as scalars (multibody.hpp
+// MB_MFMA_SCALAR_SHAPE): C5 calcDiff 25.40 -> 24.69 ms; measured neutral on the 128-thread
+// kernel and 0.5 % slower on the 256-thread all-LDS kernel, which keep the vector arguments
+#if FDDP_TU_MB == 4
+#define MB_MFMA_SCALAR_SHAPE 1
+#endif
+#include "fddp_kernels.hpp"
+#include "ktab.hpp"
+static_assert(fddp::ktab::MB_S2 == 4, "MB_MFMA_SCALAR_SHAPE is set for the MB_S2 object");
 
 namespace fddp {
 namespace ktab {

@@ -3818,6 +3818,31 @@ MB_HD inline void jac_lane(const Blk& b, const WVals& W, const double* x, int j,
 // ---- fp64 matrix-core products of the calcDiff (v_mfma_f64_16x16x4_f64) -------
 // (fragment maps and mb_mfma: with the tree-sparse LTDL above)
 typedef __attribute__((address_space(1))) double mb_glb_d;
+// The shape arguments of the two out-of-line products (nj, nc, L ...) and the wave index
+// are wave-uniform, but a function's arguments arrive in vector registers, so every loop
+// and branch over them is compiled as lane-divergent: exec-mask bookkeeping around each
+// k-chunk and each MFMA, and an s_waitcnt lgkmcnt(0) at every join. MB_MFMA_SCALAR_SHAPE
+// (set per kernel object, k_mb.hip) moves them to scalar registers on entry, and the loops
+// become scalar branches. Measured per kernel ("Round 7"): calcDiff
+// -2.8 % on mb_knot_kernel_s2 (more SGPRs: 23 -> 27 VGPR spills), none on the others.
+#ifndef MB_MFMA_SCALAR_SHAPE
+#define MB_MFMA_SCALAR_SHAPE 0
+#endif
+#if MB_MFMA_SCALAR_SHAPE
+#define MB_MFMA_UNIFORM(x) x = __builtin_amdgcn_readfirstlane(x)
+#else
+#define MB_MFMA_UNIFORM(x)
+#endif
+// (tools/mb_probe: cycles of thread 0 inside the tile loops, summed over its tiles in
+// registers: MB_TILE_LAP(k) adds the time since the last lap to sum k, after the operands
+// named in MB_TILE_PIN have arrived; MB_TILE_FLUSH(base) stores the sums and the tile count)
+#ifndef MB_TILE_DECL
+#define MB_TILE_DECL
+#define MB_TILE_START(n)
+#define MB_TILE_PIN4(a)
+#define MB_TILE_LAP(k)
+#define MB_TILE_FLUSH(base)
+#endif
 // The Fx block (euler.hxx:100-112 with JintegrateTransport / Jintegrate;
 // impulse-fwddyn.hxx:111-115) straight from the da product's accumulators:
 // da = -(Kinv_tl dtau + H da0) (contact-fwddyn.hxx:127-140 as computeABADerivatives / the
@@ -3838,7 +3863,15 @@ __device__ __attribute__((noinline)) void da_fx_mfma(const mb_lds_d* Minv, int l
                                                      int nc, int L, int mode, double dt, const mb_lds_d* Sinv, int nfd,
                                                      double* dfx, const mb_lds_d* Je, const mb_lds_d* Ai,
                                                      const mb_lds_d* Jc, double* Fx, const mb_lds_d* Z) {
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6, nw = (int)blockDim.x >> 6;
+  MB_MFMA_UNIFORM(lda);
+  MB_MFMA_UNIFORM(nj);
+  MB_MFMA_UNIFORM(nc);
+  MB_MFMA_UNIFORM(L);
+  MB_MFMA_UNIFORM(mode);
+  MB_MFMA_UNIFORM(nfd);
+  int wave = (int)threadIdx.x >> 6;
+  MB_MFMA_UNIFORM(wave);
+  const int lane = (int)threadIdx.x & 63, nw = (int)blockDim.x >> 6;
   const int li = lane & 15, lk = lane >> 4;
   const int NR = nj + nfd, tr = (NR + 15) >> 4, tc = (L + 15) >> 4, K = nj + nc, N = 2 * nj;
   const bool imp = mode & 1, integ = mode & 2, ffe = mode & 4, ok = mode & 8;
@@ -3873,8 +3906,10 @@ __device__ __attribute__((noinline)) void da_fx_mfma(const mb_lds_d* Minv, int l
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
   MB_GJ_MARK(25);
+  MB_TILE_DECL;
 #pragma unroll 1
   for (int tile = t0; tile < t1; ++tile) {
+    MB_TILE_START(1);
     const int tj = tile / tr, ti = tile - tj * tr;
     const int i = 16 * ti + li, ca = 16 * tj + li;
     const bool rv = i < nj, rf = !rv && i < NR, cv = ca < L;
@@ -3888,7 +3923,8 @@ __device__ __attribute__((noinline)) void da_fx_mfma(const mb_lds_d* Minv, int l
       // two k-ranges, each with one operand source per lane and a per-lane stride (no
       // per-step address selects, which became branches): k < nj (A = dtau, B = Kinv_tl
       // rows / H^T columns), then k' = k - nj < nc (A = da0, B = H rows / -S^-1); the
-      // padding k-steps masked; loads of 4 k-steps first, then their MFMAs
+      // padding k-steps masked in both operands (B's rows past the range are whatever the
+      // LDS holds: 0 x NaN would poison the tile); loads of 4 k-steps first, then their MFMAs
       const mb_lds_d* pa = dts + (lk * L + cac);
       const mb_lds_d* pb = rv ? Minv + (lk * lda + ic) : (rf ? H + (ir * nj + lk) : Z);
       const int sb = rv ? 4 * lda : (rf ? 4 : 0);
@@ -3900,11 +3936,15 @@ __device__ __attribute__((noinline)) void da_fx_mfma(const mb_lds_d* Minv, int l
           av[s] = pa[(k0 + 4 * s) * L];
           bw[s] = pb[(k0 / 4 + s) * sb];
         }
+        MB_TILE_PIN4(av);
+        MB_TILE_PIN4(bw);
+        MB_TILE_LAP(0);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           const int k = k0 + 4 * s + lk;
-          if (k0 + 4 * s < nj) acc = mb_mfma(cv && k < nj ? av[s] : 0., rv || rf ? bw[s] : 0., acc);
+          if (k0 + 4 * s < nj) acc = mb_mfma(cv && k < nj ? av[s] : 0., (rv || rf) && k < nj ? bw[s] : 0., acc);
         }
+        MB_TILE_LAP(1);
       }
       const mb_lds_d* qa = da0 + (lk * L + cac);
       const mb_lds_d* qb = rv ? H + (lk * nj + ic) : (rf ? Sinv + (lk * nc + ir) : Z);
@@ -3918,11 +3958,15 @@ __device__ __attribute__((noinline)) void da_fx_mfma(const mb_lds_d* Minv, int l
           av[s] = qa[(k0 + 4 * s) * L];
           bw[s] = qb[(k0 / 4 + s) * sq];
         }
+        MB_TILE_PIN4(av);
+        MB_TILE_PIN4(bw);
+        MB_TILE_LAP(0);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           const int k = k0 + 4 * s + lk;
-          if (k0 + 4 * s < nc) acc = mb_mfma(cv && k < nc ? av[s] : 0., rv || rf ? sg * bw[s] : 0., acc);
+          if (k0 + 4 * s < nc) acc = mb_mfma(cv && k < nc ? av[s] : 0., (rv || rf) && k < nc ? sg * bw[s] : 0., acc);
         }
+        MB_TILE_LAP(1);
       }
     } else {
     // (chunks of 4 k-steps: the chunk's 24 loads issued, pinned by one empty asm that
@@ -3998,7 +4042,9 @@ __device__ __attribute__((noinline)) void da_fx_mfma(const mb_lds_d* Minv, int l
       F[(int64_t)c * N + i] = fq;
       F[(int64_t)c * N + nj + i] = fv;
     }
+    MB_TILE_LAP(2);
   }
+  MB_TILE_FLUSH(32);
   MB_GJ_MARK(23);
 }
 // The Gauss-Newton blocks sc * (R^T diag(w h) R + the diagonal state / control terms)
@@ -4010,14 +4056,23 @@ __device__ __attribute__((noinline)) void da_fx_mfma(const mb_lds_d* Minv, int l
 __device__ __attribute__((noinline)) void gn_blocks_mfma(const double* Rm, int ldR, const double* wrow, int nrows,
                                                          int L, int nu, int m, double sc, double* Lxx, double* Lxu,
                                                          double* Luu, const double* diag) {
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6, nw = (int)blockDim.x >> 6;
+  MB_MFMA_UNIFORM(ldR);
+  MB_MFMA_UNIFORM(nrows);
+  MB_MFMA_UNIFORM(L);
+  MB_MFMA_UNIFORM(nu);
+  MB_MFMA_UNIFORM(m);
+  int wave = (int)threadIdx.x >> 6;
+  MB_MFMA_UNIFORM(wave);
+  const int lane = (int)threadIdx.x & 63, nw = (int)blockDim.x >> 6;
   const int li = lane & 15, lk = lane >> 4;
   const int NC = L + m, cv = L + nu, NT = (NC + 15) >> 4, ntiles = NT * (NT + 1) / 2, n = L;
   Rm = lds_ptr(Rm);
   wrow = lds_ptr(wrow);
   diag = lds_ptr(diag);
+  MB_TILE_DECL;
 #pragma unroll 1
   for (int tile = wave; tile < ntiles; tile += nw) {
+    MB_TILE_START(1);
     int bi = 0, rem = tile;
     while (rem >= NT - bi) {
       rem -= NT - bi;
@@ -4047,6 +4102,7 @@ __device__ __attribute__((noinline)) void gn_blocks_mfma(const double* Rm, int l
       asm volatile(""
                    : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(y[0]), "+v"(y[1]), "+v"(y[2]), "+v"(y[3]),
                      "+v"(wr[0]), "+v"(wr[1]), "+v"(wr[2]), "+v"(wr[3]));
+      MB_TILE_LAP(0);
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const int r = k0 + 4 * s + lk;
@@ -4054,6 +4110,7 @@ __device__ __attribute__((noinline)) void gn_blocks_mfma(const double* Rm, int l
         const double bv = (r < nrows && ca < cv) ? y[s] * wr[s] : 0.;
         if (k0 + 4 * s < nrows) acc = mb_mfma(a, bv, acc);
       }
+      MB_TILE_LAP(1);
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -4070,7 +4127,9 @@ __device__ __attribute__((noinline)) void gn_blocks_mfma(const double* Rm, int l
         if (i < j) mb_gstore(Luu + (int64_t)(i - L) * m + (j - L), v);
       }
     }
+    MB_TILE_LAP(2);
   }
+  MB_TILE_FLUSH(36);
 }
 
 // The subtree sums of the velocity-product maps (subtree_nh_lane) on the matrix cores:

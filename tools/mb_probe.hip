@@ -11,6 +11,33 @@
 #include <vector>
 // stamps inside the blocked Gauss-Jordan (multibody.hpp gj_mfma), thread 0 of workgroup 0
 __device__ unsigned long long g_gjst[32];
+// cycles inside the tile loops of the matrix-core products (multibody.hpp MB_TILE_*), thread 0
+// of workgroup 0, summed over its tiles: [32..35] the da product, [36..39] the Gauss-Newton
+// blocks: operand loads, MFMA chain, epilogue, tiles
+__device__ unsigned long long g_tile[8];
+// (the probe times the large trees' kernel, mb_knot_kernel_s2: its scalar shape arguments;
+// -DMB_MFMA_SCALAR_SHAPE=0 for the other kernels' vector arguments)
+#ifndef MB_MFMA_SCALAR_SHAPE
+#define MB_MFMA_SCALAR_SHAPE 1
+#endif
+#define MB_TILE_DECL unsigned long long mbt_p_ = 0, mbt_s_[4] = {0, 0, 0, 0}
+#define MB_TILE_START(n)                     \
+  do {                                       \
+    mbt_p_ = __builtin_amdgcn_s_memtime();   \
+    mbt_s_[3] += (n);                        \
+  } while (0)
+#define MB_TILE_PIN4(a) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]))
+#define MB_TILE_LAP(k)                                            \
+  do {                                                            \
+    const unsigned long long n_ = __builtin_amdgcn_s_memtime();   \
+    mbt_s_[k] += n_ - mbt_p_;                                     \
+    mbt_p_ = n_;                                                  \
+  } while (0)
+#define MB_TILE_FLUSH(base)                                     \
+  do {                                                          \
+    if (threadIdx.x == 0 && blockIdx.x == 0)                    \
+      for (int k_ = 0; k_ < 4; ++k_) g_tile[(base) - 32 + k_] = mbt_s_[k_]; \
+  } while (0)
 // phase labels (first stamped launch only): the source location of each phase's lambda,
 // cut from the executor method's __PRETTY_FUNCTION__ ("... (lambda at FILE:LINE:COL) ...")
 constexpr int kLabelLen = 48;
@@ -326,6 +353,11 @@ int main(int argc, char** argv) {
         for (int i = 1; i < 32; ++i)
           if (gj[i] >= gj[0] && gj[i] - gj[0] < 10000000ull) printf(" %d:%llu", i, gj[i] - gj[0]);
         printf("\n");
+        unsigned long long tl[8];
+        CK(hipMemcpyFromSymbol(tl, HIP_SYMBOL(g_tile), sizeof(tl)));
+        printf("  tile loops (thread 0's tiles; cycles in operand loads / MFMA chain / epilogue, tiles):"
+               " da %llu / %llu / %llu, %llu; gn %llu / %llu / %llu, %llu\n",
+               tl[0], tl[1], tl[2], tl[3], tl[4], tl[5], tl[6], tl[7]);
         std::vector<unsigned long long> z(32, 0ull);
         CK(hipMemcpyToSymbol(HIP_SYMBOL(g_gjst), z.data(), sizeof(gj)));
       }
