@@ -778,8 +778,9 @@ __device__ __forceinline__ bool fwd_trial(const Dev& D, int b, const ElemState& 
   for (int i = tid; i < nx; i += NT) xn[i] = x0[i];
   cost_try = 0.;
   double* dvp = out.dvp + D.knot(b, 0);
-  // (diagnostic phase timer, FDDP_STAMPS=1 on the stamps build: per wave, summed)
-  Stamp stamp(D.stamps && tid < kWave ? D.stamps + (int64_t)D.B * 128 + (int64_t)b * 8 : nullptr);  // (wave 0's)
+  // (diagnostic phase timer, FDDP_STAMPS=1 on the stamps build: per wave, summed; the records
+  // are keyed by element, so of a parallel trial group's workgroups only slot 0's records)
+  Stamp stamp(D.stamps && tid < kWave && slot == 0 ? D.stamps + (int64_t)D.B * 128 + (int64_t)b * 8 : nullptr);  // (wave 0's)
   __syncthreads();
   for (int t = 0; t <= T; ++t) {
     const int64_t kk = D.knot(b, t);
@@ -1039,7 +1040,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MB ? MBW : F
   if (threadIdx.x == 0) ss = *st;
 #ifdef FDDP_STAMPS_BUILD
   // (diagnostic: this workgroup's residency, real time and hardware ids; fddp_destroy)
-  unsigned long long* rs = D.stamps ? D.stamps + (int64_t)D.B * 136 + (int64_t)b * 4 : nullptr;
+  // (keyed by element: slot 0's workgroup only)
+  unsigned long long* rs = D.stamps && slot == 0 ? D.stamps + (int64_t)D.B * 136 + (int64_t)b * 4 : nullptr;
   if (rs && threadIdx.x == 0) {
     rs[0] = __builtin_amdgcn_s_memrealtime();
     rs[1] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11)) |

@@ -8,6 +8,13 @@
 // alignment check trips on it inlined at the 256-VGPR cap), and the calls cost the rollout
 // 6 % (29.9 -> 31.8 ms per step), more than the solve gains.
 #define MB_CALC_DENSE 1
+// the multibody-only variants keep the knot's parsed block header in scalar registers
+// (multibody.hpp MB_BLK_UNIFORM) and give every phase of the calc a fresh copy of its lane
+// index (MB_LANE_OPAQUE)
+#if defined(FDDP_TU_FWD) && FDDP_TU_FWD != 0
+#define MB_BLK_UNIFORM 1
+#define MB_LANE_OPAQUE 1
+#endif
 #include "fast_path.hpp"
 #include "fddp_kernels.hpp"
 #include "ktab.hpp"

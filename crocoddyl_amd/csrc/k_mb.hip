@@ -10,6 +10,9 @@
 #if FDDP_TU_MB == 4
 #define MB_MFMA_SCALAR_SHAPE 1
 #endif
+// (the rollout objects' MB_BLK_UNIFORM and MB_LANE_OPAQUE, k_fwd.hip, stay off in these
+// objects: on the MB_S2 kernel they cost C5 calcDiff 24.0 -> 24.6 and 24.8 ms; that object
+// is only built without the backend's loop-invariant code motion, csrc/Makefile)
 #include "fddp_kernels.hpp"
 #include "ktab.hpp"
 static_assert(fddp::ktab::MB_S2 == 4, "MB_MFMA_SCALAR_SHAPE is set for the MB_S2 object");

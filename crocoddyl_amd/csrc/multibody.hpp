@@ -96,6 +96,14 @@ MB_HD __forceinline__ T* mb_lds(T* p) {
 #endif
 }
 
+// MB_LANE_OPAQUE (per kernel object): every phase of the device executor gets its lane index
+// as a fresh register copy, so what a phase derives from it (addresses, lane masks) is formed
+// in the phase and not hoisted out of the caller's knot loop, to be held across every other
+// phase at the register cap.
+#ifndef MB_LANE_OPAQUE
+#define MB_LANE_OPAQUE 0
+#endif
+
 namespace fddp {
 namespace mb {
 
@@ -183,6 +191,57 @@ MB_HD inline Blk parse(const double* P) {
       r += (int)r[3];
     }
   }
+  return b;
+}
+
+// MB_BLK_UNIFORM (per kernel object, as MB_MFMA_SCALAR_SHAPE): the header parsed from the
+// LDS-staged block is the same in every lane, but arrives in vector registers and stays live
+// through the whole calc. parse_uniform moves every field into scalar registers (the first
+// lane's value; doubles in two halves, the LDS pointers by their 32-bit LDS address, so they
+// keep their address space). The host path is parse itself.
+#ifndef MB_BLK_UNIFORM
+#define MB_BLK_UNIFORM 0
+#endif
+#if MB_BLK_UNIFORM && defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ int mb_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ bool mb_uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
+__device__ __forceinline__ double mb_uniform(double v) {
+  int h[2];
+  __builtin_memcpy(h, &v, 8);
+  h[0] = __builtin_amdgcn_readfirstlane(h[0]);
+  h[1] = __builtin_amdgcn_readfirstlane(h[1]);
+  __builtin_memcpy(&v, h, 8);
+  return v;
+}
+__device__ __forceinline__ const double* mb_uniform(const double* p) {
+  typedef const __attribute__((address_space(3))) double* LdsP;
+  const unsigned a = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(LdsP)p);
+  return (const double*)(LdsP)(size_t)a;
+}
+#endif
+// P: the block in LDS (device)
+MB_HD __forceinline__ Blk parse_uniform(const double* P) {
+  Blk b = parse(P);
+#if MB_BLK_UNIFORM && defined(__HIP_DEVICE_COMPILE__)
+  b.dt = mb_uniform(b.dt);
+  b.nj = mb_uniform(b.nj);
+  b.nq = mb_uniform(b.nq);
+  b.nb = mb_uniform(b.nb);
+  b.ff = mb_uniform(b.ff);
+  b.ncost = mb_uniform(b.ncost);
+  b.g = mb_uniform(b.g);
+  b.arm = mb_uniform(b.arm);
+  b.J = mb_uniform(b.J);
+  b.C = mb_uniform(b.C);
+  b.nun = mb_uniform(b.nun);
+  b.ncon = mb_uniform(b.ncon);
+  b.nc = mb_uniform(b.nc);
+  b.damping = mb_uniform(b.damping);
+  b.K = mb_uniform(b.K);
+  b.impulse = mb_uniform(b.impulse);
+  b.r_coeff = mb_uniform(b.r_coeff);
+  b.enable_force = mb_uniform(b.enable_force);
+#endif
   return b;
 }
 
@@ -438,7 +497,11 @@ struct DevExec {
   int nt;
   template <class F>
   __device__ __forceinline__ void run(F f) const {
+#if MB_LANE_OPAQUE
+    [[clang::always_inline]] f(mb_launder((int)threadIdx.x));
+#else
     [[clang::always_inline]] f((int)threadIdx.x);
+#endif
     __syncthreads();
   }
   template <class F>
@@ -1813,13 +1876,18 @@ MB_HD inline int count_cost_rows(const Blk& b, int nu) {
 // [row0, row0 + nc) (lam unread for an inactive contact: lambda = 0):
 //   contact force: lambda_i - fref_i (contact-force.hxx:33-50: jMf.actInv(f) is the multiplier);
 //   friction cone: A_i . lambda_lin (contact-friction-cone.hxx:58)
-MB_HD __forceinline__ double force_res(const CRec& C, const double* lam, int i) {
+// (lam(k): multiplier k, so that the calc reads it where it lies, sign applied at the use)
+template <class L>
+MB_HD __forceinline__ double force_res_at(const CRec& C, L lam, int i) {
   const double* d = C.d();
   const int row0 = (int)d[0];
-  if (C.type() == C_CONTACT_FORCE) return (row0 >= 0 ? lam[row0 + i] : 0.) - d[2 + i];
+  if (C.type() == C_CONTACT_FORCE) return (row0 >= 0 ? lam(row0 + i) : 0.) - d[2 + i];
   if (row0 < 0) return 0.;
   const double* A = d + 3 + 3 * i;
-  return A[0] * lam[row0] + A[1] * lam[row0 + 1] + A[2] * lam[row0 + 2];
+  return A[0] * lam(row0) + A[1] * lam(row0 + 1) + A[2] * lam(row0 + 2);
+}
+MB_HD __forceinline__ double force_res(const CRec& C, const double* lam, int i) {
+  return force_res_at(C, [lam](int k) { return lam[k]; }, i);
 }
 // row i of a force cost's Jacobian column from the multiplier Jacobian column
 // dl[row * ld] (the same linear map as force_res, without the offset)
@@ -1831,11 +1899,15 @@ MB_HD __forceinline__ double force_jac(const CRec& C, const double* dl, int64_t 
   return A[0] * dl[(int64_t)row0 * ld] + A[1] * dl[(int64_t)(row0 + 1) * ld] + A[2] * dl[(int64_t)(row0 + 2) * ld];
 }
 // activation value of a force cost (inactive contact: lambda = 0)
-MB_HD inline double force_cost_activation(const Blk& b, const CRec& C, const double* lam, int nu) {
+template <class L>
+MB_HD __forceinline__ double force_cost_activation_at(const Blk& b, const CRec& C, L lam, int nu) {
   const Act act = cost_act(b, C, nu);
   double a = 0.;
-  for (int e = 0; e < act.nr; ++e) a += act.value2(e, force_res(C, lam, e));
+  for (int e = 0; e < act.nr; ++e) a += act.value2(e, force_res_at(C, lam, e));
   return 0.5 * a;
+}
+MB_HD inline double force_cost_activation(const Blk& b, const CRec& C, const double* lam, int nu) {
+  return force_cost_activation_at(b, C, [lam](int k) { return lam[k]; }, nu);
 }
 
 // Residual of a frame cost, value only (calc). Returns the residual size.
@@ -1998,7 +2070,9 @@ MB_HD __attribute__((always_inline)) inline void contact_a0_position(const Blk& 
   double r[6] = {0., 0., 0., 0., 0., 0.};
   if (kp != 0.) frame_residual_value(b, W, C, r);
   const int n = C.type() == C_CONTACT_3D ? 3 : 6;
-  for (int e = 0; e < n; ++e) a0[e] = kp * r[e];
+#pragma unroll
+  for (int e = 0; e < 6; ++e)  // fixed trip count: r stays in registers
+    if (e < n) a0[e] = kp * r[e];
 }
 MB_HD __attribute__((always_inline)) inline void contact_a0_drift(const Blk& b, const WVals& W, const CRec& C, double* a0) {
   const double* d = C.d();
@@ -2723,7 +2797,7 @@ MB_HD __forceinline__
 void calc_cost_records(const double* P_, double* w_, double* parts_, const double* x_, const double* ub_, double* cv_,
                        int sl, int snt) {
   const double* P = mb_lds(P_);
-  const Blk b = parse(P);
+  const Blk b = parse_uniform(P);
   const WVals W{mb_lds(w_), b.nj, mb_lds(parts_)};
   const double* x = mb_lds(x_);
   const double* ub = mb_lds(ub_);
@@ -2765,7 +2839,7 @@ MB_HD __forceinline__ double knot_calc_x(const X& ex, const double* P, int nx, c
                                 double* xnext, double* w) {
   w = ex.lds(w);  // the work area and the parameter block live in LDS
   P = ex.lds(P);
-  const Blk b = parse(P);
+  const Blk b = parse_uniform(P);
   const bool imp = b.impulse;  // impulse: [M | Jc^T] only, z = v
   const int nj = b.nj, nq = b.nq, nc = b.nc, nu = nj - b.nun, ncol = imp ? nj + nc : nj + nc + 1;
   const int lda = lda_of(nj);
@@ -2877,9 +2951,9 @@ MB_HD __forceinline__ double knot_calc_x(const X& ex, const double* P, int nx, c
         for (int k = 0; k < kf; ++k) cr += CRec{cr}.size();
         const CRec C{cr};
         if (force_cost(C.type())) {
-          double lamv[kMaxNc];
-          for (int k = 0; k < nc; ++k) lamv[k] = -S[(int64_t)nc * nc + k];
-          cv[kf] = C.weight() * force_cost_activation(b, C, lamv, nu);
+          // lambda = -S's last column, read where it lies (no private copy)
+          const double* Sl = S + (int64_t)nc * nc;
+          cv[kf] = C.weight() * force_cost_activation_at(b, C, [Sl](int k) { return -Sl[k]; }, nu);
         }
       }
       if (lane >= nj) return;
@@ -2943,7 +3017,7 @@ MB_HD __forceinline__ double knot_calc_dense_x(const X& ex, const double* P, int
                                                bool use_u, double* xnext, double* w) {
   w = ex.lds(w);
   P = ex.lds(P);
-  const Blk b = parse(P);
+  const Blk b = parse_uniform(P);
   const bool imp = b.impulse;  // impulse: [M | Jc^T] only, z = v
   const int nj = b.nj, nq = b.nq, nc = b.nc, nu = nj - b.nun, ncol = imp ? nj + nc : nj + nc + 1;
   const int lda = lda_of(nj);
@@ -3076,9 +3150,9 @@ MB_HD __forceinline__ double knot_calc_dense_x(const X& ex, const double* P, int
         for (int k = 0; k < kf; ++k) cr += CRec{cr}.size();
         const CRec C{cr};
         if (force_cost(C.type())) {
-          double lamv[kMaxNc];
-          for (int k = 0; k < nc; ++k) lamv[k] = -S[(int64_t)nc * nc + k];
-          cv[kf] = C.weight() * force_cost_activation(b, C, lamv, nu);
+          // lambda = -S's last column, read where it lies (no private copy)
+          const double* Sl = S + (int64_t)nc * nc;
+          cv[kf] = C.weight() * force_cost_activation_at(b, C, [Sl](int k) { return -Sl[k]; }, nu);
         }
       }
       if (lane >= nj) return;
@@ -4185,7 +4259,7 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
                                    double* cost_out = nullptr, const double* xu_pre = nullptr, int spill = 0) {
   w = ex.lds(w);  // the work area and the parameter block live in LDS
   P = ex.lds(P);
-  const Blk b = parse(P);
+  const Blk b = parse_uniform(P);
   const bool imp = b.impulse;  // ActionModelImpulseFwdDynamics (impulse-fwddyn.hxx:53-127)
   const int nj = b.nj, nq = b.nq, n = 2 * nj, L = 2 * nj, nc = b.nc, nu = nj - b.nun;
   const int lda = lda_of(nj);
