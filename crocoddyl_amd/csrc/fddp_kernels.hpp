@@ -509,7 +509,6 @@ __device__ __forceinline__ bool bwd_sweep(const Dev& D, int b, bool feas, double
       for (int i = tid; i < n; i += NT) D.dQx[r * D.sN + i] = S.qx[i];
       for (int e = tid; e < n * m; e += NT) D.dQxu[r * D.sNM + e] = (e / n < nu) ? S.Qxu[e] : 0.;
       for (int e = tid; e < m * m; e += NT) D.dQuu[r * D.sMM + e] = (e % m < nu && e / m < nu) ? S.Quu[e] : 0.;
-      for (int i = tid; i < m; i += NT) D.dQu[r * D.sM + i] = i < nu ? S.qu[i] : 0.;
     }
     __syncthreads();
     if (nu && feas && D.box_knot(b, t)) {
@@ -559,6 +558,10 @@ __device__ __forceinline__ bool bwd_sweep(const Dev& D, int b, bool feas, double
       }
       __syncthreads();
     }
+    // Qu's debug copy after the gains: the box QP zeroes its clamped entries (Qu_[t] as the
+    // reference leaves it, box-fddp.cpp:76-78)
+    if (D.dQu)
+      for (int i = tid; i < m; i += NT) D.dQu[D.run(b, t) * D.sM + i] = i < nu ? S.qu[i] : 0.;
     if (nu) {
       // store K, k ; Quuk = Quu k
       {

@@ -487,6 +487,8 @@ struct BoxQP {
   BoxQPSolution sol;
   std::vector<int> inv_idx;  // the free set sol.Hff_inv was factorised on (harness)
   int iters = 0;  // Newton iterations run by the last solve (diagnostic)
+  bool fixed_point = false;  // the last solve's line search accepted no alpha (harness)
+  bool converged = false;    // the last solve returned from its convergence test, not at maxiter (harness)
 
   // box-qp.cpp:14-46 (alphas 2^-k, k = 0..9)
   void init(int n, int mi, double ta, double tg, double rg) {
@@ -507,6 +509,8 @@ struct BoxQP {
     inv_idx.clear();
     for (int i = 0; i < n; ++i) x[i] = std::max(std::min(xinit[i], ub[i]), lb[i]);  // :89-91
     iters = 0;
+    fixed_point = false;
+    converged = false;
     for (int k = 0; k < maxiter; ++k) {
       sol.clamped_idx.clear();
       sol.free_idx.clear();
@@ -536,6 +540,7 @@ struct BoxQP {
           inv_idx = sol.free_idx;
         }
         sol.x = x;
+        converged = true;
         return true;
       }
       ++iters;
@@ -577,6 +582,7 @@ struct BoxQP {
       for (int i = 0; i < nf; ++i) dx[sol.free_idx[i]] = dxf[i];
       // line search (:178-189)
       const double fold = 0.5 * dot(x.data(), Hx.data(), n) + dot(q, x.data(), n);
+      fixed_point = true;  // until a step is accepted: x unchanged, every later iteration repeats this one
       for (double a : alphas) {
         for (int i = 0; i < n; ++i) xnew[i] = std::max(std::min(x[i] + a * dx[i], ub[i]), lb[i]);
         gemv(H.a.data(), n, n, xnew.data(), Hxn.data());
@@ -585,6 +591,7 @@ struct BoxQP {
         for (int i = 0; i < n; ++i) gd += g[i] * (x[i] - xnew[i]);
         if (fold - fnew > th_acceptstep * gd) {
           x = xnew;
+          fixed_point = false;
           break;
         }
       }
@@ -621,6 +628,13 @@ struct Solver {
   std::vector<char> haslim;       // has_control_limits per running knot
   std::vector<Mat> Quu_inv;
   BoxQP qp;
+  // the box QPs of the last backward pass, per running knot (harness, read-only):
+  // ran, Newton iterations, free mask of the solution, mask Hff_inv was factorised on,
+  // line search at its fixed point, returned from the convergence test
+  struct BoxRec {
+    uint64_t ran = 0, iters = 0, free_mask = 0, inv_mask = 0, fixed_point = 0, converged = 0;
+  };
+  std::vector<BoxRec> box_rec;
   // bookkeeping for the harness
   int status = FDDP_STATUS_RUNNING;
   int n_iter_run = 0;
@@ -686,6 +700,7 @@ struct Solver {
     ulb.assign(T, Vec(nu, -INFINITY));
     uub.assign(T, Vec(nu, INFINITY));
     haslim.assign(T, 0);
+    box_rec.assign(T, BoxRec());
   }
 
   // per-knot buffers after the model at knot t changed (fddp_set_knots):
@@ -754,7 +769,15 @@ struct Solver {
       dlb[i] = ulb[t][i] - us[t][i];
       dub[i] = uub[t][i] - us[t][i];
     }
-    if (!qp.solve(Quu[t], Qu[t].data(), dlb.data(), dub.data(), k[t].data())) return false;
+    const bool qp_ok = qp.solve(Quu[t], Qu[t].data(), dlb.data(), dub.data(), k[t].data());
+    BoxRec& rec = box_rec[t];
+    rec.ran = 1;
+    rec.iters = (uint64_t)qp.iters;
+    rec.fixed_point = qp.fixed_point ? 1 : 0;
+    rec.converged = qp.converged ? 1 : 0;
+    for (int i : qp.sol.free_idx) rec.free_mask |= 1ull << i;
+    for (int i : qp.inv_idx) rec.inv_mask |= 1ull << i;
+    if (!qp_ok) return false;
     const BoxQPSolution& sol = qp.sol;
     // Quu_inv(free_i, free_j) = Hff_inv(i, j). Hff_inv is the one of the last
     // Newton iteration; when the QP converges at k > 0 the free set may have
@@ -823,6 +846,7 @@ struct Solver {
   bool backwardPass() {
     const int T = P->T, n = P->ndx;
     const Data& dT = P->datas[T];
+    box_rec.assign(T, BoxRec());
     Vxx[T].a = dT.Lxx.a;
     Vx[T] = dT.Lx;
     if (!std::isnan(xreg))
@@ -1566,6 +1590,23 @@ int oracle_get_quu_inv(oracle_handle* h, double* out) {
   for (int b = 0; b < D.B; ++b)
     for (int t = 0; t < D.T; ++t)
       std::memcpy(out + ((size_t)b * D.T + t) * m * m, h->solvers[b].Quu_inv[t].a.data(), sizeof(double) * m * m);
+  return FDDP_OK;
+}
+// The box QPs of the last backward pass (tests only, no libfddp_hip counterpart):
+// out[(b*T + t)*6 + ...] = ran, Newton iterations, free mask, inverse mask, fixed point, converged.
+int oracle_get_box_record(oracle_handle* h, uint64_t* out) {
+  const fddp_dims& D = h->dims;
+  for (int b = 0; b < D.B; ++b)
+    for (int t = 0; t < D.T; ++t) {
+      const Solver::BoxRec& r = h->solvers[b].box_rec[t];
+      uint64_t* o = out + ((size_t)b * D.T + t) * 6;
+      o[0] = r.ran;
+      o[1] = r.iters;
+      o[2] = r.free_mask;
+      o[3] = r.inv_mask;
+      o[4] = r.fixed_point;
+      o[5] = r.converged;
+    }
   return FDDP_OK;
 }
 // Batched BoxQP, same contract as fddp_boxqp_solve.

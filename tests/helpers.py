@@ -149,6 +149,7 @@ class Gpu:
 
     def set_solver_kind(self, kind):
         self._ok(self.L.fddp_set_solver_kind(self.h, int(kind)))
+        self.box = int(kind) == _abi.SOLVER_BOXFDDP
 
     def set_control_limits(self, lb, ub):
         la = None if lb is None else np.ascontiguousarray(lb, dtype=np.float64)
@@ -179,12 +180,14 @@ def start(name, S):
 ALL_BLOCKS = ("Fx", "Fu", "Lxx", "Lxu", "Luu", "Lx", "Lu", "fs")
 
 
-def phases(h, xs, us, alphas, xreg, blocks=("Fx", "Fu", "Lxx", "Lx", "fs")):
+def phases(h, xs, us, alphas, xreg, blocks=("Fx", "Fu", "Lxx", "Lx", "fs"), feasible=False):
     """calcDiff, backwardPass, forwardPass(alpha) for each alpha, from a fresh solver state.
-    blocks: the calcDiff outputs read back (ALL_BLOCKS: every one)."""
+    blocks: the calcDiff outputs read back (ALL_BLOCKS: every one). feasible: what
+    set_candidate is told of (xs, us). A handle in SolverBoxFDDP mode (set_solver_kind)
+    has its Quu_inv read back too."""
     d = h.dims
     n, m = d.ndx, d.nu_max
-    h.set_candidate(xs, us, False)
+    h.set_candidate(xs, us, feasible)
     h.set_solver_state(it=0, xreg=xreg, ureg=xreg)
     out = {"cost": h.ddp_calc_diff()}
     for name, q, per in (("Fx", _abi.Q_FX, n * n), ("Fu", _abi.Q_FU, n * m), ("Lxx", _abi.Q_LXX, n * n),
@@ -196,12 +199,45 @@ def phases(h, xs, us, alphas, xreg, blocks=("Fx", "Fu", "Lxx", "Lx", "fs")):
     for name, q, nk, per in (("K", _abi.Q_K, d.T, m * n), ("k", _abi.Q_KV, d.T, m), ("Vxx", _abi.Q_VXX, d.T + 1, n * n),
                              ("Vx", _abi.Q_VX, d.T + 1, n), ("Qu", _abi.Q_QU, d.T, m), ("Quu", _abi.Q_QUU, d.T, m * m)):
         out[name] = h.quantity(q, nk, per)
+    if getattr(h, "box", False):
+        out["Quu_inv"] = h.quu_inv()
     for a in alphas:
         rc, ct, st = h.forward_pass(a)
         assert rc == 0
         out[f"cost_try@{a}"], out[f"fwd_status@{a}"] = ct, st
         out[f"xs_try@{a}"], out[f"us_try@{a}"] = h.xs(trial=True), h.us(trial=True)
     return out
+
+
+def live(S, out):
+    """`out` (helpers.phases / a solve's us) with the control entries beyond each knot's
+    own nu zeroed (running knots with nu < nu_max, the terminal knot)."""
+    d = S["dims"]
+    n, m = d.ndx, d.nu_max
+    nus = [k[1] for k in S["knots"]]
+    nus[-1] = 0
+    res = dict(out)
+    for key, a in out.items():
+        name = key.split("@")[0]
+        if name not in ("Lxu", "Luu", "Lu", "K", "k", "Qu", "Quu", "us", "us_try"):
+            continue
+        a = np.array(a, copy=True)
+        for t in range(a.shape[1]):
+            nu = nus[t]
+            if nu == m:
+                continue
+            if name == "Lxu":  # ndx x nu, column-major
+                a[:, t].reshape(-1, m, n)[:, nu:, :] = 0.0
+            elif name in ("Luu", "Quu"):  # nu x nu, leading dimension nu_max
+                v = a[:, t].reshape(-1, m, m)
+                v[:, nu:, :] = 0.0
+                v[:, :, nu:] = 0.0
+            elif name == "K":  # nu x ndx, leading dimension nu_max
+                a[:, t].reshape(-1, n, m)[:, :, nu:] = 0.0
+            else:
+                a[:, t, nu:] = 0.0
+        res[key] = a
+    return res
 
 
 def rel_err(a, b):

@@ -70,6 +70,8 @@ def _bind(L):
     L.oracle_get_phase_times.argtypes = [C.c_void_p, _abi.D, C.c_int]
     L.oracle_get_quu_inv.restype = C.c_int
     L.oracle_get_quu_inv.argtypes = [C.c_void_p, _abi.D]
+    L.oracle_get_box_record.restype = C.c_int
+    L.oracle_get_box_record.argtypes = [C.c_void_p, _abi.U64]
     L.oracle_boxqp_solve.restype = C.c_int
     L.oracle_boxqp_solve.argtypes = [C.c_int, C.c_int, _abi.D, _abi.D, _abi.D, _abi.D, _abi.D,
                                      C.POINTER(_abi.BoxQPParams), _abi.D, _abi.U64, _abi.U64, _abi.D, _abi.I32,
@@ -228,6 +230,7 @@ class Oracle:
     # SolverBoxFDDP
     def set_solver_kind(self, kind):
         self.L.oracle_set_solver_kind(self.h, int(kind))
+        self.box = int(kind) == _abi.SOLVER_BOXFDDP
 
     def set_control_limits(self, lb, ub):
         la = None if lb is None else np.ascontiguousarray(lb, dtype=np.float64)
@@ -239,6 +242,18 @@ class Oracle:
         a = np.zeros((d.B, d.T, d.nu_max * d.nu_max))
         self.L.oracle_get_quu_inv(self.h, _abi.dptr(a))
         return a
+
+    def box_record(self):
+        """The box QPs of the last backward pass, (B, T) arrays: ran (bool), iters (Newton
+        iterations), free_mask (the solution's free set), inv_mask (the set Hff_inv was
+        factorised on), fixed_point (the line search accepted no step), converged (returned
+        from the convergence test, not at maxiter). Oracle only: the library keeps no such
+        record."""
+        d = self.dims
+        a = np.zeros((d.B, d.T, 6), dtype=np.uint64)
+        self.L.oracle_get_box_record(self.h, a.ctypes.data_as(_abi.U64))
+        return dict(ran=a[:, :, 0] != 0, iters=a[:, :, 1].astype(np.int64), free_mask=a[:, :, 2].copy(),
+                    inv_mask=a[:, :, 3].copy(), fixed_point=a[:, :, 4] != 0, converged=a[:, :, 5] != 0)
 
 
 def default_params():

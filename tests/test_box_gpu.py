@@ -5,6 +5,10 @@ counts and regularisation (branch decisions bit-identical), xs/us/cost
 within 1e-6 relative; box-QP solutions within 1e-9. Every solver test runs
 on each device code path (8-wave MFMA sweep + fast path, 4-wave MFMA sweep +
 generic kernels, generic sweep) through the backward_variant fixture.
+
+The problems here are dense synthetic knots on a Euclidean state. SolverBoxFDDP on
+multibody horizons (contact dynamics, free-flyer states, per-knot limit patterns, the
+multibody rollouts and the grouped line search) lives in tests/test_box_multibody_gpu.py.
 """
 import numpy as np
 import pytest
@@ -64,6 +68,105 @@ def test_boxqp_batched_vs_oracle(n):
         assert np.max(np.abs(s.Hff_inv - ref)) <= 1e-9 * max(1.0, np.max(np.abs(ref)))
         active += len(s.clamped_idx)
     assert active > 0
+
+
+def _gpu_boxqp(H, q, lb, ub, xinit, prm):
+    """fddp_boxqp_solve with the call shape of oracle_lib.boxqp_solve."""
+    import ctypes as C
+
+    from crocoddyl_amd._lib import lib
+    H = np.asarray(H, float)
+    B, n = H.shape[0], H.shape[1]
+    Hc = np.ascontiguousarray(H.transpose(0, 2, 1))
+    vs = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, float), (B, n))) for v in (q, lb, ub, xinit)]
+    out = dict(x=np.zeros((B, n)), free_mask=np.zeros(B, np.uint64), inv_mask=np.zeros(B, np.uint64),
+               Hinv=np.zeros((B, n, n)), status=np.zeros(B, np.int32))
+    rc = lib().fddp_boxqp_solve(0, B, n, _abi.dptr(Hc), *[_abi.dptr(v) for v in vs], C.byref(prm), _abi.dptr(out["x"]),
+                                out["free_mask"].ctypes.data_as(_abi.U64), out["inv_mask"].ctypes.data_as(_abi.U64),
+                                _abi.dptr(out["Hinv"]), out["status"].ctypes.data_as(_abi.I32))
+    assert rc == 0
+    out["Hinv"] = np.ascontiguousarray(out["Hinv"].transpose(0, 2, 1))
+    return out
+
+
+def _same_qp(tag, g, o):
+    """x, free_mask, inv_mask, Hff_inv and status of a batch, library vs oracle (1e-9 as
+    test_boxqp_batched_vs_oracle). A QP that threw has no other output."""
+    np.testing.assert_array_equal(g["status"], o["status"], err_msg=tag)
+    ok = o["status"] == 0
+    np.testing.assert_array_equal(g["free_mask"][ok], o["free_mask"][ok], err_msg=tag + " free_mask")
+    np.testing.assert_array_equal(g["inv_mask"][ok], o["inv_mask"][ok], err_msg=tag + " inv_mask")
+    for b in np.flatnonzero(ok):
+        assert np.max(np.abs(g["x"][b] - o["x"][b])) <= 1e-9 * max(1.0, np.max(np.abs(o["x"][b]))), (tag, b)
+        assert np.max(np.abs(g["Hinv"][b] - o["Hinv"][b])) <= 1e-9 * max(1.0, np.max(np.abs(o["Hinv"][b]))), (tag, b)
+
+
+def _bits(n):
+    return np.uint64((1 << n) - 1)
+
+
+@pytest.mark.parametrize("n", [1, 2, 16, 17, 63, 64])
+def test_boxqp_edges_vs_oracle(n):
+    """fddp_boxqp_solve at its edges (one variable, the wave's 64, the sizes around the 16
+    tiles), each size in one batch of: no bounds; lb == ub everywhere (free set empty at
+    k = 0) and on some variables; xinit outside the bounds; xinit exactly on active bounds;
+    an indefinite H (status 1); a QP whose first Newton step clamps every variable (free
+    set empty at k > 0). Then the same batch at maxiter 0 and 1, and the reference's known
+    failure: with reg != 0 the line search prices the regularised step with the true H and
+    rejects every alpha (the fixed point). What each case is there for is asserted on the
+    oracle first."""
+    rng = np.random.default_rng(900 + n)
+    R = 4  # random draws of each case
+    H, q, lb, ub, x0 = _random_qps(rng, 7 * R, n)
+    case = np.repeat(np.arange(7), R)
+    lb[case == 0], ub[case == 0] = -np.inf, np.inf
+    lb[case == 1] = rng.uniform(-1, 1, (R, n))
+    ub[case == 1] = lb[case == 1]
+    some = rng.random((R, n)) < 0.5
+    some[:, 0] = True
+    lb[case == 2] = np.where(some, ub[case == 2], lb[case == 2])
+    x0[case == 3] = np.where(rng.random((R, n)) < 0.5, 5.0, -5.0)
+    lb[case == 3] = rng.uniform(-1.0, -0.1, (R, n))  # (all finite: every entry of xinit is outside)
+    # on active bounds: xinit = lb with a gradient that pushes further down (odd variables: interior)
+    lb[case == 4] = rng.uniform(-1.0, -0.1, (R, n))
+    x0[case == 4] = lb[case == 4]
+    x0[case == 4, 1::2] = 0.0
+    q[case == 4] = np.abs(H[case == 4]).sum(axis=2) + 1.0
+    H[case == 5] = H[case == 5] - 2.0 * np.max(np.linalg.eigvalsh(H[case == 5]), axis=1)[:, None, None] * np.eye(n)
+    lb[case == 5], ub[case == 5] = -1.0, 1.0  # (bounded, so the first free set is every variable: the LLT fails at once)
+    x0[case == 5] = 0.0
+    H[case == 6] = np.eye(n)
+    q[case == 6], lb[case == 6], ub[case == 6], x0[case == 6] = -10.0, -1.0, 1.0, 0.0
+    prm = _qp_params(th_grad=1e-9, reg=0.0)
+    o = oracle_lib.boxqp_solve(H, q, lb, ub, x0, prm)
+    # what the cases are there for, on the oracle
+    assert (o["status"][case != 5] == 0).all() and (o["status"][case == 5] == 1).all()
+    assert (o["free_mask"][case == 0] == _bits(n)).all()
+    assert (o["free_mask"][case == 1] == 0).all() and (o["iters"][case == 1] == 0).all()
+    assert (o["free_mask"][case == 2] != _bits(n)).all()
+    assert np.all(o["x"][case == 3] >= lb[case == 3]) and np.all(o["x"][case == 3] <= ub[case == 3])
+    assert all(int(m) & 1 == 0 for m in o["free_mask"][case == 4])  # variable 0 stays on its bound
+    assert (o["free_mask"][case == 6] == 0).all() and (o["inv_mask"][case == 6] == _bits(n)).all()
+    assert (o["iters"][case == 6] == 1).all() and np.all(o["x"][case == 6] == 1.0)
+    _same_qp(f"n={n}", _gpu_boxqp(H, q, lb, ub, x0, prm), o)
+    keep = case != 5
+    for maxiter in (0, 1):
+        prm = _qp_params(maxiter=maxiter, th_grad=1e-9, reg=0.0)
+        o = oracle_lib.boxqp_solve(H[keep], q[keep], lb[keep], ub[keep], x0[keep], prm)
+        assert (o["iters"] <= maxiter).all()
+        if maxiter == 1:  # QPs that took their one Newton step return without a convergence test
+            assert (o["iters"] == 1).any()
+        _same_qp(f"n={n} maxiter={maxiter}", _gpu_boxqp(H[keep], q[keep], lb[keep], ub[keep], x0[keep], prm), o)
+    # the known failure: H = I, no bounds, xinit halfway to the optimum -q; the regularised
+    # Newton point -q / (1 + reg) lies on the other side of xinit, so every step raises the cost
+    reg = 9.0
+    qf = rng.uniform(0.5, 2.0, (R, n)) * rng.choice([-1.0, 1.0], (R, n))
+    Hf = np.repeat(np.eye(n)[None], R, axis=0)
+    inf = np.full((R, n), np.inf)
+    prm = _qp_params(th_grad=1e-9, reg=reg)
+    o = oracle_lib.boxqp_solve(Hf, qf, -inf, inf, -0.5 * qf, prm)
+    assert (o["status"] == 0).all() and (o["iters"] == prm.maxiter).all() and np.array_equal(o["x"], -0.5 * qf)
+    _same_qp(f"n={n} fixed point", _gpu_boxqp(Hf, qf, -inf, inf, -0.5 * qf, prm), o)
 
 
 def test_boxqp_known_answers_gpu():

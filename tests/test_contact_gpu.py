@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import helpers
+import variant_cases as vc
 from crocoddyl_amd import _abi, multibody as mb, synthetic
 from crocoddyl_amd.problem import pack_problem
 from oracle import fddp_np
@@ -20,12 +21,7 @@ pytestmark = pytest.mark.gpu
 SOLVE_TOL = 1e-8  # element-wise (helpers.elem_err), solves vs the numpy oracle
 
 
-def _mixed(T, B, seed=0):
-    """Free-flight knots (ActuationModelFull, nu = 7) for the first half of the
-    horizon, then gripper-contact knots (floating-base actuation, nu = 6)."""
-    x0s, run_c, term_c = synthetic.build_arm_contact(T=T, B=B, seed=seed, contact="6d")
-    _, run_f, _ = synthetic.build_arm(T=T, B=B, dt=1e-2, w_x=1e-2, w_u=1e-2)
-    return x0s, run_f[:T // 2] + run_c[T // 2:], term_c
+_mixed = vc.mixed_arm
 
 
 def _setup(T, B, mixed=False, impact=None, **kw):

@@ -53,35 +53,7 @@ def _setenv(monkeypatch, env):
         monkeypatch.setenv(k, str(v))
 
 
-def _live(S, out):
-    """`out` (helpers.phases / a solve's us) with the control entries beyond each knot's
-    own nu zeroed (running knots with nu < nu_max, the terminal knot)."""
-    d = S["dims"]
-    n, m = d.ndx, d.nu_max
-    nus = [k[1] for k in S["knots"]]
-    nus[-1] = 0
-    res = dict(out)
-    for key, a in out.items():
-        name = key.split("@")[0]
-        if name not in ("Lxu", "Luu", "Lu", "K", "k", "Qu", "Quu", "us", "us_try"):
-            continue
-        a = np.array(a, copy=True)
-        for t in range(a.shape[1]):
-            nu = nus[t]
-            if nu == m:
-                continue
-            if name == "Lxu":  # ndx x nu, column-major
-                a[:, t].reshape(-1, m, n)[:, nu:, :] = 0.0
-            elif name in ("Luu", "Quu"):  # nu x nu, leading dimension nu_max
-                v = a[:, t].reshape(-1, m, m)
-                v[:, nu:, :] = 0.0
-                v[:, :, nu:] = 0.0
-            elif name == "K":  # nu x ndx, leading dimension nu_max
-                a[:, t].reshape(-1, n, m)[:, :, nu:] = 0.0
-            else:
-                a[:, t, nu:] = 0.0
-        res[key] = a
-    return res
+_live = helpers.live
 
 
 _REF = {}  # (problem key, xreg) -> (oracle phases, floors or None): shared by the cases of one problem

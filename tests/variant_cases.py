@@ -47,6 +47,14 @@ def build(name):
     return x0s, [run_c[0], run_f[0], run_c[0], run_f[0]], term_c
 
 
+def mixed_arm(T, B, seed=0):
+    """Free-flight knots (ActuationModelFull, nu = 7) for the first half of the
+    horizon, then gripper-contact knots (floating-base actuation, nu = 6)."""
+    x0s, run_c, term_c = synthetic.build_arm_contact(T=T, B=B, seed=seed, contact="6d")
+    _, run_f, _ = synthetic.build_arm(T=T, B=B, dt=1e-2, w_x=1e-2, w_u=1e-2)
+    return x0s, run_f[:T // 2] + run_c[T // 2:], term_c
+
+
 def setup(x0s, running, terminal):
     """helpers.setup's dict for a model list."""
     B = x0s.shape[0]
