@@ -28,8 +28,11 @@
 #include "fast_path.hpp"
 #include "bwd_mfma.hpp"
 #include "ktab.hpp"
+#include "launch_plan.hpp"
 
 using namespace fddp;
+using plan::block_doubles;
+using plan::mb_block_check;
 
 // ---- kernel-table dispatchers (ktab.hpp): variant -> the object that compiled it ----
 namespace fddp {
@@ -108,185 +111,6 @@ int fail(int code, const std::string& msg) {
     if (e_ != hipSuccess) return fail(FDDP_ERR_RUNTIME, std::string("launch: ") + hipGetErrorString(e_)); \
   } while (0)
 
-int64_t block_doubles(int kind, int nx, int nu) {
-  switch (kind) {
-    case FDDP_KNOT_LQR:
-      return FDDP_PARAM_HEADER + 2LL * nx * nx + 2LL * nx * nu + (int64_t)nu * nu + 2LL * nx + nu;
-    case FDDP_KNOT_UNICYCLE:
-      return FDDP_PARAM_HEADER;
-    case FDDP_KNOT_EULER_DIFFLQR: {
-      const int64_t nq = nx / 2;
-      return FDDP_PARAM_HEADER + 2 * nq * nq + nq * nu + nq + (int64_t)nx * nx + (int64_t)nx * nu +
-             (int64_t)nu * nu + nx + nu;
-    }
-  }
-  return -1;
-}
-
-
-// Checks one FDDP_KNOT_EULER_FREEFWD / _CONTACTFWD / FDDP_KNOT_IMPULSEFWD block
-// (layouts in include/fddp_hip.h) against nx / nu and the space left in the
-// pool. Returns its size in doubles, or -1 with `why` set. nj / njac / nc:
-// dofs, jac costs and contact rows (LDS sizing).
-int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, int nu, std::string& why, int* nj_out,
-                       int* njac_out, int* nc_out, bool* vcols_out = nullptr, int* nu_out = nullptr,
-                       int* nrows_out = nullptr) {
-  using namespace fddp::mb;
-  if (avail < FDDP_PARAM_HEADER) return why = "block out of range", -1;
-  const double dt = P[0];
-  const int nj = (int)P[1], ncost = (int)P[2];
-  const int64_t size = (int64_t)P[3];
-  if (!(dt >= 0.) || !std::isfinite(dt)) return why = "dt has positive value", -1;
-  if ((double)nj != P[1] || nj < 1 || nj > kMaxJ) return why = "number of dofs out of [1, 64]", -1;
-  if (size > avail || (double)size != P[3]) return why = "block out of range", -1;
-  int64_t o = FDDP_PARAM_HEADER + 3 + nj;
-  if (o + kJRec > size) return why = "block too small for its joints", -1;
-  const bool ff = (int)P[o] == J_FREEFLYER;
-  if (ff && nj < 6) return why = "a free-flyer root needs nv >= 6", -1;
-  const int nb = ff ? nj - 5 : nj, nq = ff ? nj + 1 : nj;
-  if (nx != nq + nj) return why = "multibody knots need nx = nq + nv", -1;
-  const bool contact = kind == FDDP_KNOT_EULER_CONTACTFWD, impulse = kind == FDDP_KNOT_IMPULSEFWD;
-  if (!contact && !impulse && (nu != nj || ff)) return why = "ActuationModelFull needs nu = nv and no free-flyer", -1;
-  if (impulse && nu != 0) return why = "impulse knots have nu = 0", -1;
-  if (impulse && dt != 0.) return why = "impulse blocks carry dt = 0 (no integrator)", -1;
-  if ((double)ncost != P[2] || ncost < 0 || ncost > kMaxCosts) return why = "number of costs out of [0, 64]", -1;
-  int force_rows = 0;  // rows the contact-force costs read
-  if (o + (int64_t)kJRec * nb > size) return why = "block too small for its joints", -1;
-  for (int i = 0; i < nb; ++i) {
-    const double* J = P + o + (int64_t)kJRec * i;
-    const int type = (int)J[0], par = (int)J[1];
-    if ((double)type != J[0] || (type != J_REVOLUTE && type != J_FREEFLYER)) return why = "unknown joint type", -1;
-    if (type == J_FREEFLYER && (i != 0 || par != -1)) return why = "a free-flyer may only be the root joint", -1;
-    if ((double)par != J[1] || par < -1 || par >= i) return why = "joint parents must precede their children", -1;
-    if (type == J_REVOLUTE) {
-      const double an = std::sqrt(J[2] * J[2] + J[3] * J[3] + J[4] * J[4]);
-      if (!(std::fabs(an - 1.) < 1e-9)) return why = "joint axes must be unit vectors", -1;
-    }
-    if (!(J[17] >= 0.)) return why = "negative body mass", -1;
-  }
-  o += (int64_t)kJRec * nb;
-  int njac = 0;
-  bool vcols = false;
-  for (int k = 0; k < ncost; ++k) {
-    if (o + kCHdr > size) return why = "cost records out of range", -1;
-    const double* C = P + o;
-    const int type = (int)C[0];
-    const int64_t rs = (int64_t)C[3];
-    const int act = (int)C[2];
-    if ((double)act != C[2] || act < A_QUAD || act > A_WEIGHTED_QUAD_BARRIER)
-      return why = "unknown activation kind", -1;
-    const int ap = act <= A_WEIGHTED_QUAD ? 1 : (act == A_QUAD_BARRIER ? 2 : 3);  // parameter rows per residual
-    int64_t want = -1;
-    if (type == C_STATE) want = kCHdr + nx + ap * 2 * nj;
-    if (type == C_CONTROL) want = kCHdr + nu + ap * (int64_t)nu;
-    if (type == C_FRAME_PLACEMENT) want = kCHdr + 25 + ap * 6;
-    if (type == C_FRAME_TRANSLATION) want = kCHdr + 16 + ap * 3;
-    if (type == C_FRAME_VELOCITY) {
-      if (impulse) return why = "frame-velocity costs are covered on Euler knots only", -1;
-      want = kCHdr + 19 + ap * 6;
-    }
-    if (type == C_COM_POSITION) want = kCHdr + 3 + ap * 3;
-    if (type == C_CONTACT_FORCE || type == C_FRICTION_CONE) {
-      // [row0, nr, fref(6)] | [row0, nc, nr, A(3 nr)]; rows checked against the contacts below
-      if (kind != FDDP_KNOT_EULER_CONTACTFWD) return why = "force costs need contact knots", -1;
-      if (o + kCHdr + 3 > size) return why = "cost records out of range", -1;
-      const int row0 = (int)C[kCHdr];
-      if ((double)row0 != C[kCHdr] || (row0 < 0 && row0 != kInactiveForceRow))
-        return why = "contact-force cost row out of range", -1;
-      if (type == C_CONTACT_FORCE) {
-        const int nrf = (int)C[kCHdr + 1];
-        if (nrf != 3 && nrf != 6) return why = "contact-force costs need a 3- or 6-row force", -1;
-        want = kCHdr + 8 + ap * nrf;
-        if (row0 >= 0) force_rows = std::max(force_rows, row0 + nrf);
-      } else {
-        const int ncc = (int)C[kCHdr + 1], nrc = (int)C[kCHdr + 2];
-        if ((double)nrc != C[kCHdr + 2] || nrc < 1 || nrc > 6) return why = "friction cone rows out of [1, 6]", -1;
-        if (row0 >= 0 && ncc != 3 && ncc != 6) return why = "friction cone on a contact of 3 or 6 rows", -1;
-        want = kCHdr + 3 + 3 * nrc + ap * nrc;
-        if (row0 >= 0) force_rows = std::max(force_rows, row0 + ncc);
-      }
-    }
-    if (want < 0) return why = "unknown cost type " + std::to_string(type), -1;
-    if (rs != want || o + rs > size) return why = "cost record of the wrong size", -1;
-    if (type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_FRAME_VELOCITY) {
-      const int fj = (int)C[kCHdr];
-      if ((double)fj != C[kCHdr] || fj < 0 || fj >= nb) return why = "frame attached to an unknown joint", -1;
-    }
-    if (type == C_STATE && ff)  // the reference state's free-flyer pose must be finite
-      for (int e = 0; e < 7; ++e)
-        if (!std::isfinite(C[kCHdr + e])) return why = "non-finite reference state", -1;
-    if (type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_COM_POSITION ||
-        type == C_FRAME_VELOCITY || (type == C_STATE && ff))
-      ++njac;
-    if (type == C_FRAME_VELOCITY) vcols = true;
-    o += rs;
-  }
-  int nc = 0;
-  std::vector<std::pair<int, int>> crow;  // (row0, rows) of every contact record
-  if (contact || impulse) {  // [nun | r_coeff, damping, ncontact, 0 | 1 | 2] + contact / impulse records
-    if (o + 4 > size) return why = "contact section out of range", -1;
-    const int nun = (int)P[o], ncon = (int)P[o + 2];
-    const double damping = P[o + 1];
-    if (impulse ? P[o + 3] != 1. : (P[o + 3] != 0. && P[o + 3] != 2.))
-      return why = "contact / impulse section flag does not match the kind", -1;
-    if (impulse) {
-      if (!(P[o] >= 0.) || !std::isfinite(P[o])) return why = "The restitution coefficient has to be positive", -1;
-    } else {
-      if ((double)nun != P[o] || nun < 0 || nun >= nj) return why = "unactuated dofs out of [0, nv)", -1;
-      if (ff && nun != 6) return why = "ActuationModelFloatingBase on a free-flyer leaves 6 dofs unactuated", -1;
-      if (nu != nj - nun) return why = "ActuationModelFloatingBase needs nu = nv - nun", -1;
-    }
-    if (!(damping >= 0.) || !std::isfinite(damping)) return why = "The damping factor has to be positive", -1;
-    if ((double)ncon != P[o + 2] || ncon < 0) return why = "negative number of contacts", -1;
-    o += 4;
-    for (int k = 0; k < ncon; ++k) {
-      if (o + kCHdr + 1 > size) return why = "contact records out of range", -1;
-      const double* C = P + o;
-      const int type = (int)C[0];
-      const int64_t rs = (int64_t)C[3];
-      int64_t want = -1;
-      if (type == C_CONTACT_3D) want = kCHdr + (impulse ? 13 : 16);
-      if (type == C_CONTACT_6D) want = kCHdr + (impulse ? 13 : 25);
-      if (want < 0) return why = "unknown contact type " + std::to_string(type), -1;
-      if (rs != want || o + rs > size) return why = "contact record of the wrong size", -1;
-      const int fj = (int)C[kCHdr];
-      if ((double)fj != C[kCHdr] || fj < 0 || fj >= nb) return why = "contact frame attached to an unknown joint", -1;
-      if (!std::isfinite(C[1]) || !std::isfinite(C[2])) return why = "non-finite contact gains", -1;
-      const int rows = type == C_CONTACT_3D ? 3 : 6;
-      crow.emplace_back(nc, rows);
-      nc += rows;
-      o += rs;
-    }
-    if (nc > kMaxNc) return why = "more than 24 contact rows in one knot", -1;
-  }
-  if (force_rows > nc) return why = "contact-force cost reads rows beyond the contacts", -1;
-  if (force_rows > 0) {  // each contact-force cost reads exactly one contact of its size
-    int64_t oc = FDDP_PARAM_HEADER + 3 + nj + (int64_t)kJRec * nb;
-    for (int k = 0; k < ncost; ++k) {
-      const double* C = P + oc;
-      if (((int)C[0] == C_CONTACT_FORCE || (int)C[0] == C_FRICTION_CONE) && (int)C[kCHdr] >= 0) {
-        bool hit = false;
-        for (const auto& r : crow) hit = hit || (r.first == (int)C[kCHdr] && r.second == (int)C[kCHdr + 1]);
-        if (!hit) return why = "a force cost must read one whole contact of its size", -1;
-      }
-      oc += (int64_t)C[3];
-    }
-  }
-  if (o != size) return why = "block size does not match its records", -1;
-  if (njac > kMaxJacCosts) return why = "more than 8 frame / CoM / frame-velocity / free-flyer state costs in one knot", -1;
-  const int nrows = count_cost_rows(parse(P), nu);
-  if (nrows > kMaxCostRows) return why = "more than 64 cost residual rows with dense Jacobians in one knot", -1;
-  if ((pad2(diff_layout(nj, njac, nc, vcols, nu, nrows).total) + pad2(size)) * 8 > 160 * 1024)
-    return why = "too many dofs for the calcDiff LDS plan", -1;
-  if (nj_out) *nj_out = std::max(*nj_out, nj);
-  if (njac_out) *njac_out = std::max(*njac_out, njac);
-  if (nc_out) *nc_out = std::max(*nc_out, nc);
-  if (vcols_out) *vcols_out = *vcols_out || vcols;
-  if (nu_out) *nu_out = std::max(*nu_out, nu);
-  if (nrows_out) *nrows_out = std::max(*nrows_out, nrows);
-  return size;
-}
-
 // Validation of a knot sequence against the handle's dims (fddp_create,
 // fddp_set_knots, fddp_set_model_params). exact_nu_max: the running knots' max
 // nu must equal nu_max (creation); otherwise it may be smaller (the
@@ -336,23 +160,37 @@ int check_knots(const fddp_dims& d, const fddp_knot_desc* knots, const double* p
   return FDDP_OK;
 }
 
+// The override variables of launch_plan.hpp, read per handle (A/B runs, the variant tests):
+// CROCODDYL_AMD_LS_PAR at creation (`prev` null), the others at every apply_knots.
+plan::Overrides read_overrides(const plan::Overrides* prev) {
+  auto env = [](const char* name) { return std::getenv(name); };
+  auto env_int = [&](const char* name, int unset) { return env(name) ? std::atoi(env(name)) : unset; };
+  auto is0 = [&](const char* name) { return env(name) && env(name)[0] == '0' ? 1 : 0; };
+  plan::Overrides o;
+  if (env("FDDP_MB_W1")) o.mb_w1 = is0("FDDP_MB_W1") ? 0 : 1;
+  o.mb_nt = env_int("FDDP_MB_NT", 0);
+  o.mb_spill = env_int("FDDP_MB_SPILL", -1);
+  o.fwd_mb_off = is0("FDDP_FWD_MB");
+  o.fwd_mbw = env_int("FDDP_FWD_MBW", 0);
+  if (const char* ew = env("FDDP_BWD_WAVES")) o.bwd_waves = ew[0] == '1' ? 1 : (ew[0] == '4' ? 4 : 8);
+  o.bwd_generic = env("FDDP_BACKWARD") && std::strcmp(env("FDDP_BACKWARD"), "generic") == 0;
+  o.fast_off = is0("FDDP_FAST");
+  if (prev)
+    o.ls_par = prev->ls_par;
+  else if (env("CROCODDYL_AMD_LS_PAR"))  // (1 is the serial line search)
+    o.ls_par = std::max(1, std::min(16, env_int("CROCODDYL_AMD_LS_PAR", 0)));
+  return o;
+}
+
 }  // namespace
 
 struct fddp_handle_s {
   fddp_dims dims;
   int device = 0;
-  int npar_env = 0;    // CROCODDYL_AMD_LS_PAR (0: chosen per problem)
+  int cus = 0;         // the device's compute units
+  plan::LaunchPlan plan;  // kernel variants, LDS sizes and overrides of the knots (launch_plan.hpp; apply_knots)
   int npar_alloc = 1;  // trial slots allocated for the parallel line search
-  bool npar_adapt = false;  // trial-group size re-chosen after every solve (choose_npar)
   bool npar_chosen = false;  // choose_npar has set D.npar
-  double ls_slots = 0.;     // rollout workgroups resident on the device at once
-  int fwd_mb_variant = -1;  // rollout_variant's choice (-1: not yet made; reset by apply_knots)
-  // variant overrides read from the environment by apply_knots (unset: the rules decide)
-  int env_mb_w1 = -1;           // FDDP_MB_W1: 0 / 1 forces the 2- / 1-wave/EU calcDiff build
-  int env_mb_nt = 0;            // FDDP_MB_NT: 128 / 256 / 512 forces the calcDiff workgroup size
-  int env_mb_spill = -1;        // FDDP_MB_SPILL: 0 forces the all-LDS calcDiff plan
-  bool env_fwd_mb_off = false;  // FDDP_FWD_MB=0: the generic rollout on multibody horizons
-  int env_fwd_mbw = 0;          // FDDP_FWD_MBW: 2 / 3 forces the rollout's waves/EU build
   hipStream_t stream = nullptr;
   std::vector<fddp_knot_desc> knots;
   int64_t n_params = 0;
@@ -373,16 +211,8 @@ struct fddp_handle_s {
   double* d_uub = nullptr;
   unsigned char* d_haslim = nullptr;
   int64_t bytes = 0;
-  size_t bwd_smem = 0, fwd_smem = 0, calc_smem = 0, cdiff_smem = 0;
-  bool fast = false;  // dense-knot fast path (fast_path.hpp) for calc / calcDiff / forward
-  size_t fused_smem = 0, fwd_fast_smem = 0;
-  int64_t pcap = 0;  // doubles of LDS reserved for a resident parameter block
-  bool has_mb = false;     // multibody knots present (mb_knot_kernel)
-  bool all_mb = false;     // every knot is a multibody knot
-  size_t mb_diff_smem = 0; // its dynamic LDS
-  int mb_nj = 0;            // largest multibody tree (dofs)
-  int bwd_variant = 0;  // 0 generic, else (NTL*10+MTL)*10+waves of the MFMA sweep
-  int ls_npar_last = 0;      // trial-group size of the last line search (1: serial)
+  size_t bwd_smem = 0;  // the generic sweep's dynamic LDS (from the dims alone: fddp_create)
+  int ls_npar_last = 0;     // trial-group size of the last line search (1: serial)
   std::vector<int> h_order;  // host copy of D.ls_order (kept alive for the async upload)
   int ls_launches_last = 0;  // rollout (forward_kernel) dispatches of the last line search
   fddp_iteration_callback cb = nullptr;  // per-iteration callback (fddp_set_callback)
@@ -482,42 +312,25 @@ BoxQPCfg to_boxcfg(const fddp_boxqp_params& p) {
 int launch_fused(fddp_handle* h, int sel_calc, int sel_diff, int gaps) {
   Timed tm(h, sel_diff >= 0 ? 1 : 0);
   const Dev& D = h->D;
-  KLAUNCH(ktab::calc_tiled(dim3(D.B), h->fused_smem, h->stream, D, sel_calc, sel_diff, gaps, h->pcap));
+  KLAUNCH(ktab::calc_tiled(dim3(D.B), h->plan.lds.fused_smem, h->stream, D, sel_calc, sel_diff, gaps, h->plan.lds.pcap));
   return FDDP_OK;
-}
-// The knot-parallel kernel's LDS plan leaves room for one workgroup per CU: take the
-// 1-wave/EU build (no spills; FDDP_MB_W1=0 forces the 2-wave one, for A/B runs).
-static bool mb_one_per_cu(const fddp_handle* h) {
-  return h->env_mb_w1 >= 0 ? h->env_mb_w1 == 1 : h->mb_diff_smem > 80 * 1024;
-}
-// 512-thread (8-wave) workgroups for the one-per-CU plans: two waves per SIMD where the
-// 256-thread plan has one (C5 calcDiff 66 -> 59 ms); FDDP_MB_NT=256 / 512 forces
-static bool mb_x8(const fddp_handle* h) { return h->env_mb_nt ? h->env_mb_nt == 512 : mb_one_per_cu(h); }
-// 128-thread (2-wave) workgroups for the small trees whose LDS plan fits four per CU
-static bool mb_x2(const fddp_handle* h) {
-  return h->env_mb_nt ? h->env_mb_nt == 128 : (h->mb_nj <= 16 && h->mb_diff_smem <= 40 * 1024);
-}
-// The knot-parallel kernel's variant (ktab::MB_*) for the handle's LDS plan
-static int mb_variant(const fddp_handle* h) {
-  return h->D.mbspill ? ktab::MB_S2
-                      : mb_x2(h) ? ktab::MB_X2 : (mb_x8(h) ? ktab::MB_X8 : (mb_one_per_cu(h) ? ktab::MB_W1 : ktab::MB_W2));
 }
 // Multibody knots (knot-parallel): calc for sel_calc, calcDiff for sel_diff (-1: none).
 int launch_mb(fddp_handle* h, int sel_calc, int sel_diff) {
   const Dev& D = h->D;
-  KLAUNCH(ktab::mb_knot(mb_variant(h), dim3(D.T + 1, D.B), h->mb_diff_smem, h->stream, D, sel_calc, sel_diff));
+  KLAUNCH(ktab::mb_knot(h->plan.var.mb, dim3(D.T + 1, D.B), h->plan.lds.mb_diff_smem, h->stream, D, sel_calc, sel_diff));
   return FDDP_OK;
 }
 int launch_calc(fddp_handle* h, int sel) {
-  if (h->fast) return launch_fused(h, sel, -1, 0);
+  if (h->plan.lds.fast) return launch_fused(h, sel, -1, 0);
   Timed tm(h, 0);
   const Dev& D = h->D;
-  if (h->has_mb) {
+  if (h->plan.lds.has_mb) {
     int rc;
     if ((rc = launch_mb(h, sel, -1))) return rc;
-    if (!h->all_mb) KLAUNCH(ktab::calc(dim3(D.B), h->calc_smem, h->stream, D, sel, h->pcap, 1));
+    if (!h->plan.lds.all_mb) KLAUNCH(ktab::calc(dim3(D.B), h->plan.lds.calc_smem, h->stream, D, sel, h->plan.lds.pcap, 1));
   } else {
-    KLAUNCH(ktab::calc(dim3(D.B), h->calc_smem, h->stream, D, sel, h->pcap, 0));
+    KLAUNCH(ktab::calc(dim3(D.B), h->plan.lds.calc_smem, h->stream, D, sel, h->plan.lds.pcap, 0));
   }
   return FDDP_OK;
 }
@@ -528,33 +341,33 @@ int launch_cost_sum(fddp_handle* h, int sel, double* out) {
   return FDDP_OK;
 }
 int launch_calc_diff(fddp_handle* h, int sel, int gaps) {
-  if (h->fast) return launch_fused(h, -1, sel, gaps);
+  if (h->plan.lds.fast) return launch_fused(h, -1, sel, gaps);
   Timed tm(h, 1);
   const Dev& D = h->D;
-  if (h->has_mb) {  // multibody knots: one workgroup per knot, before the gaps pass
+  if (h->plan.lds.has_mb) {  // multibody knots: one workgroup per knot, before the gaps pass
     int rc;
     if ((rc = launch_mb(h, -1, sel))) return rc;
   }
-  KLAUNCH(ktab::calc_diff(dim3(D.B), h->cdiff_smem, h->stream, D, sel, gaps, h->pcap));
+  KLAUNCH(ktab::calc_diff(dim3(D.B), h->plan.lds.cdiff_smem, h->stream, D, sel, gaps, h->plan.lds.pcap));
   return FDDP_OK;
 }
 // problem.calc (sel_calc) + cost_ = sum of knot costs, then problem.calcDiff
 // (sel_diff, + gaps): one fused pass on the fast path.
 int launch_calc_then_diff(fddp_handle* h, int sel_calc, int sel_calc_sum, int sel_diff, int gaps) {
   int rc;
-  if (h->fast) {
+  if (h->plan.lds.fast) {
     if ((rc = launch_fused(h, sel_calc, sel_diff, gaps))) return rc;
     return launch_cost_sum(h, sel_calc_sum, nullptr);
   }
-  if (h->has_mb) {  // multibody knots: their calc fused into the knot-parallel calcDiff
+  if (h->plan.lds.has_mb) {  // multibody knots: their calc fused into the knot-parallel calcDiff
     // one timer record per calcDiff call (class 1): the knot-parallel kernel, the
     // dense knots' calc (mixed horizons only), the cost sum and the gaps pass
     Timed tm(h, 1);
     const Dev& D = h->D;
     if ((rc = launch_mb(h, sel_calc, sel_diff))) return rc;
-    if (!h->all_mb) KLAUNCH(ktab::calc(dim3(D.B), h->calc_smem, h->stream, D, sel_calc, h->pcap, 1));
+    if (!h->plan.lds.all_mb) KLAUNCH(ktab::calc(dim3(D.B), h->plan.lds.calc_smem, h->stream, D, sel_calc, h->plan.lds.pcap, 1));
     if ((rc = launch_cost_sum(h, sel_calc_sum, nullptr))) return rc;
-    KLAUNCH(ktab::calc_diff(dim3(D.B), h->cdiff_smem, h->stream, D, sel_diff, gaps, h->pcap));
+    KLAUNCH(ktab::calc_diff(dim3(D.B), h->plan.lds.cdiff_smem, h->stream, D, sel_diff, gaps, h->plan.lds.pcap));
     return FDDP_OK;
   }
   if ((rc = launch_calc(h, sel_calc))) return rc;
@@ -564,8 +377,8 @@ int launch_calc_then_diff(fddp_handle* h, int sel_calc, int sel_calc_sum, int se
 int launch_backward(fddp_handle* h, int mode) {
   Timed tm(h, 2);
   const Dev& D = h->D;
-  if (h->bwd_variant)
-    KLAUNCH(ktab::backward_mfma(h->bwd_variant, dim3(D.B), h->stream, D, to_prm(h->prm), mode));
+  if (h->plan.var.bwd)
+    KLAUNCH(ktab::backward_mfma(h->plan.var.bwd, dim3(D.B), h->stream, D, to_prm(h->prm), mode));
   else
     KLAUNCH(ktab::backward_generic(dim3(D.B), h->bwd_smem, h->stream, D, to_prm(h->prm), mode));
   return FDDP_OK;
@@ -588,55 +401,14 @@ static int ensure_par_slots(fddp_handle* h) {
   return FDDP_OK;
 }
 
-// every knot multibody: the rollout variant with only the multibody calc compiled in
-// (FDDP_FWD_MB=0 selects the generic one, for A/B runs)
-static bool mb_rollout(const fddp_handle* h) { return h->all_mb && !h->env_fwd_mb_off; }
-
-// Workgroups of `fn` one CU holds at once with `smem` bytes of dynamic LDS: the occupancy
-// API's answer, capped by the LDS allocated in 2 KB granules (measured on gfx950,
-// tools/occ_probe.hip: 53,248 B per workgroup fit three per CU, 53,776 B two, where the API
-// still says three).
-static int resident_per_cu(const void* fn, size_t smem) {
-  int per_cu = 0;
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kNT, smem);
-  hipFuncAttributes fa{};
-  (void)hipFuncGetAttributes(&fa, fn);
-  const size_t g = 2048, lds = ((smem + fa.sharedSizeBytes + g - 1) / g) * g;
-  const int by_lds = lds > 0 ? (int)((160 * 1024) / lds) : per_cu;
-  return std::max(1, std::min(per_cu, by_lds));
-}
-// The rollout variant: the generic one for mixed horizons; for multibody-only horizons the
-// three-workgroups-per-CU build (168 VGPRs, spills) when its LDS allows three per CU and the
-// batch needs more than two per CU, else the 256-VGPR build (FDDP_FWD_MBW=2|3 forces one).
-static int rollout_variant(fddp_handle* h) {
-  if (!mb_rollout(h)) return ktab::FWD_GENERIC;
-  if (h->fwd_mb_variant >= 0) return h->fwd_mb_variant;
-  const int env = h->env_fwd_mbw;
-  int dev_cus = 0;
-  (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, h->device);
-  const bool three = resident_per_cu(ktab::forward_fn(ktab::FWD_MB), h->fwd_smem) >= 3;
-  const bool take3 = env ? env == 3 : (three && h->D.B > 2 * std::max(1, dev_cus));
-  h->fwd_mb_variant = take3 ? ktab::FWD_MB : ktab::FWD_MB2;
-  return h->fwd_mb_variant;
-}
-
 // Trial-group size of the next line searches from the trial counts of the last one
 // (the results are bit-identical for every size; only the work and the number of
 // sequential launches change). With S rollout workgroups resident at once and t_b the
 // trials element b needed: serial (1) takes ~max(sum t_b / S, max t_b) trial-times, one
 // group launch per g trials ~sum_k max(U_k / S, 1) with U_k the trial slots of group k.
 static void choose_npar(fddp_handle* h, const std::vector<ElemState>& st) {
-  if (!h->npar_adapt || h->fast) return;
+  if (!h->plan.lds.npar_adapt || h->plan.lds.fast) return;
   const int na = h->prm.n_alphas;
-  if (h->ls_slots <= 0.) {
-    int dev_cus = 0;
-    (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, h->device);
-    const int per_cu = resident_per_cu(ktab::forward_fn(rollout_variant(h)), h->fwd_smem);
-    h->ls_slots = (double)std::max(1, dev_cus) * std::max(1, per_cu);
-    if (std::getenv("FDDP_STAMPS"))  // (diagnostic runs: the rollout's residency)
-      std::fprintf(stderr, "[fddp] rollout: %d workgroups per CU x %d CUs (LDS %zu B per workgroup)\n", per_cu, dev_cus,
-                   h->fwd_smem);
-  }
   std::vector<int> t;
   t.reserve(st.size());
   for (const ElemState& s : st) {
@@ -652,7 +424,7 @@ static void choose_npar(fddp_handle* h, const std::vector<ElemState>& st) {
   if (t.empty()) return;
   // (in whole rounds of resident workgroups: a launch with one workgroup more than the
   // slots takes two trial-times)
-  const double S = h->ls_slots;
+  const double S = h->plan.var.ls_slots;
   double best = 0.;
   int best_g = 1;
   for (int g : {1, 2, 4}) {
@@ -684,7 +456,7 @@ static void choose_npar(fddp_handle* h, const std::vector<ElemState>& st) {
 static int update_ls_order(fddp_handle* h, const std::vector<ElemState>& st) {
   Dev& D = h->D;
   const int B = D.B, na = h->prm.n_alphas;
-  if (B < 2 || h->fast) return FDDP_OK;
+  if (B < 2 || h->plan.lds.fast) return FDDP_OK;
   if (!D.ls_order) {
     double* p = nullptr;
     int rc;
@@ -715,7 +487,7 @@ static int update_ls_order(fddp_handle* h, const std::vector<ElemState>& st) {
 int launch_forward(fddp_handle* h, int mode, double alpha, int* count) {
   Timed tm(h, 3);
   const Dev& D = h->D;
-  if (!h->fast && mode == 0 && D.npar > 1) {
+  if (!h->plan.lds.fast && mode == 0 && D.npar > 1) {
     // the line search in groups of npar trials evaluated together; every group
     // is launched (decided elements exit at once), so there is no host round trip
     int rc;
@@ -723,9 +495,9 @@ int launch_forward(fddp_handle* h, int mode, double alpha, int* count) {
     const int na = h->prm.n_alphas, G = (na + D.npar - 1) / D.npar;
     h->ls_npar_last = D.npar;
     h->ls_launches_last = G;
-    const int v = rollout_variant(h);
+    const int v = h->plan.var.fwd;
     for (int g = 0; g < G; ++g) {
-      KLAUNCH(ktab::forward(v, dim3(D.B, D.npar), h->fwd_smem, h->stream, D, to_prm(h->prm), 2, 1., nullptr, h->pcap,
+      KLAUNCH(ktab::forward(v, dim3(D.B, D.npar), h->plan.lds.fwd_smem, h->stream, D, to_prm(h->prm), 2, 1., nullptr, h->plan.lds.pcap,
                             g));
       KLAUNCH(ktab::ls_select(dim3(D.B), h->stream, D, to_prm(h->prm), g, g == G - 1 ? 1 : 0, count));
     }
@@ -735,12 +507,12 @@ int launch_forward(fddp_handle* h, int mode, double alpha, int* count) {
     h->ls_npar_last = 1;
     h->ls_launches_last = 1;
   }
-  if (h->fast)
-    KLAUNCH(ktab::forward(ktab::FWD_FAST, dim3(D.B), h->fwd_fast_smem, h->stream, D, to_prm(h->prm), mode, alpha,
-                          count, h->pcap, 0));
+  if (h->plan.lds.fast)
+    KLAUNCH(ktab::forward(ktab::FWD_FAST, dim3(D.B), h->plan.lds.fwd_fast_smem, h->stream, D, to_prm(h->prm), mode, alpha,
+                          count, h->plan.lds.pcap, 0));
   else
-    KLAUNCH(ktab::forward(rollout_variant(h), dim3(D.B), h->fwd_smem, h->stream, D,
-                          to_prm(h->prm), mode, alpha, count, h->pcap, 0));
+    KLAUNCH(ktab::forward(h->plan.var.fwd, dim3(D.B), h->plan.lds.fwd_smem, h->stream, D,
+                          to_prm(h->prm), mode, alpha, count, h->plan.lds.pcap, 0));
   return FDDP_OK;
 }
 
@@ -832,138 +604,29 @@ void fddp_default_params(fddp_params* p) {
 
 namespace {
 
-// Knot-dependent device state of a handle: LDS plans and the fast-path
-// choice, the parameter pool, the knot descriptors, the knot segments of the
-// tiled calc, and the Riccati sweep variant (fddp_create, fddp_set_knots).
+// Knot-dependent device state of a handle: the launch plan (launch_plan.hpp), the parameter
+// pool, the knot descriptors and the knot segments of the tiled calc (fddp_create,
+// fddp_set_knots).
 int apply_knots(fddp_handle* h, const fddp_knot_desc* knots, const double* params, int64_t n_params) {
   Dev& D = h->D;
   const fddp_dims& d = h->dims;
   const int64_t K1 = (int64_t)d.T + 1;
   int rc;
   h->knots.assign(knots, knots + K1);
-  {  // the variant overrides (A/B runs, the variant tests), per handle like FDDP_FAST below
-    auto env_int = [](const char* name, int unset) {
-      const char* e = std::getenv(name);
-      return e ? std::atoi(e) : unset;
-    };
-    const char* w1 = std::getenv("FDDP_MB_W1");
-    h->env_mb_w1 = w1 ? (w1[0] == '0' ? 0 : 1) : -1;
-    h->env_mb_nt = env_int("FDDP_MB_NT", 0);
-    h->env_mb_spill = env_int("FDDP_MB_SPILL", -1);
-    const char* fm = std::getenv("FDDP_FWD_MB");
-    h->env_fwd_mb_off = fm && fm[0] == '0';
-    h->env_fwd_mbw = env_int("FDDP_FWD_MBW", 0);
-  }
-  {
-    int64_t pmax = 0;
-    int mb_nj = 0, mb_njac = 0, mb_nc = 0;
-    bool mb_vcols = false;
-    int mb_nu = 0, mb_nrows = 0;
-    // each multibody block's own shape: the device lays out a knot's calcDiff LDS from its
-    // own block, so the plan to allocate is the largest knot's, not the plan of the largest
-    // value of every parameter (on the Solo12 trot those come from different knots: 82.2 KB,
-    // one workgroup per CU, against the largest knot's 79.6 KB)
-    struct MbShape {
-      int nj, njac, nc, nu, nrows;
-      bool vcols;
-    };
-    std::vector<MbShape> shapes;
-    h->has_mb = false;
-    for (int t = 0; t <= d.T; ++t) {
-      int64_t sz;
-      if (is_mb_kind(knots[t].kind)) {
-        h->has_mb = true;
-        sz = 0;
-        const int nb = knots[t].param_stride > 0 ? d.B : 1;
-        for (int b = 0; b < nb; ++b) {  // validated by check_knots
-          const int64_t off = knots[t].param_offset + (int64_t)b * knots[t].param_stride;
-          std::string why;
-          MbShape k{0, 0, 0, 0, 0, false};
-          sz = std::max(sz, mb_block_check(params + off, n_params - off, knots[t].kind, d.nx, knots[t].nu, why, &k.nj,
-                                           &k.njac, &k.nc, &k.vcols, &k.nu, &k.nrows));
-          mb_nj = std::max(mb_nj, k.nj);
-          mb_njac = std::max(mb_njac, k.njac);
-          mb_nc = std::max(mb_nc, k.nc);
-          mb_vcols = mb_vcols || k.vcols;
-          mb_nu = std::max(mb_nu, k.nu);
-          mb_nrows = std::max(mb_nrows, k.nrows);
-          bool seen = false;
-          for (const MbShape& q : shapes)
-            seen = seen || (q.nj == k.nj && q.njac == k.njac && q.nc == k.nc && q.nu == k.nu && q.nrows == k.nrows &&
-                            q.vcols == k.vcols);
-          if (!seen) shapes.push_back(k);
-        }
-      } else {
-        sz = block_doubles(knots[t].kind, d.nx, knots[t].nu);
-      }
-      pmax = std::max<int64_t>(pmax, sz);
-    }
-    h->all_mb = true;
-    for (int t = 0; t <= d.T; ++t) h->all_mb = h->all_mb && is_mb_kind(knots[t].kind);
-    D.mbw = h->has_mb ? pad2(fddp::mb::calc_work_doubles(mb_nj, mb_nc)) : 0;
-    D.mbw_fwd = h->has_mb ? pad2(fddp::mb::calc_dense_doubles(mb_nj, mb_nc)) : 0;
-    h->mb_nj = mb_nj;
-    // parallel line-search trials: they pay on the large trees (C5 Talos, nv = 38:
-    // forward -12 %), where one rollout keeps a CU busy longest; on small ones (C4
-    // Solo12, nv = 18) the extra trials cost more than the shorter chains save
-    // (a re-application of the knots — fddp_set_knots, the MPC loop's circularAppend —
-    // keeps the size chosen from the last line search's trial counts: resetting it every
-    // step cost the C5 shift protocol's rollout 52.3 -> 65.8 ms)
-    if (!(h->npar_chosen && h->has_mb && !h->npar_env))
-      D.npar = h->npar_env ? h->npar_env : (h->has_mb && mb_nj >= 24 ? 4 : 1);
-    h->npar_adapt = !h->npar_env && h->has_mb;
-    int64_t mb_pmax = 0;  // largest multibody parameter block (staged in LDS by mb_knot_kernel)
-    for (int t = 0; t <= d.T; ++t)
-      if (is_mb_kind(knots[t].kind)) {
-        const int nb = knots[t].param_stride > 0 ? d.B : 1;
-        for (int b = 0; b < nb; ++b)
-          mb_pmax = std::max<int64_t>(mb_pmax, (int64_t)params[knots[t].param_offset + (int64_t)b * knots[t].param_stride + 3]);
-      }
-    // the calcDiff's LDS plan: spilled to the output blocks where the all-LDS plan would
-    // leave room for one workgroup per CU only (multibody.hpp diff_spill; FDDP_MB_SPILL=0
-    // forces the all-LDS plan, for A/B runs)
-    const int spill_env = h->env_mb_spill;
-    auto plan_doubles = [&](int spill) {  // the largest knot's plan under spill flags `spill`
-      int64_t mx = 0;
-      for (const MbShape& q : shapes)
-        mx = std::max<int64_t>(mx, pad2(fddp::mb::diff_layout(q.nj, q.njac, q.nc, q.vcols, q.nu, q.nrows, spill).total));
-      return mx;
-    };
-    // (the spill flags themselves from the largest value of every parameter: the spilled
-    // arrays must fit their output blocks on every knot)
-    D.mbspill = h->has_mb && spill_env != 0 && (plan_doubles(0) + pad2(mb_pmax)) * 8 > 80 * 1024
-                    ? fddp::mb::diff_spill(mb_nj, mb_njac, mb_nc, mb_vcols, mb_nu, mb_nrows, mb_pmax, D.m)
-                    : 0;
-    D.mbd = h->has_mb ? plan_doubles(D.mbspill) : 0;
-    h->mb_diff_smem = h->has_mb ? sizeof(double) * (D.mbd + pad2(mb_pmax)) : 0;
-    const int64_t budget = (150 * 1024) / 8 - (2 * D.sX + D.sM + 2 * D.sN + 5 * (kNT / kWave) + 16) - D.mbw;
-    // LDS-staged parameter blocks up to pcap doubles; larger (dense) blocks are read from
-    // global memory. The multibody calc reads its block from LDS only (knots.hpp), so
-    // pcap covers at least the largest multibody block.
-    h->pcap = pmax <= budget ? pad2(pmax) : (pad2(mb_pmax) <= budget ? pad2(mb_pmax) : 0);
-    if (h->has_mb && h->pcap < pad2(mb_pmax))
-      return fail(FDDP_ERR_INVALID_ARG, "multibody parameter blocks exceed the LDS budget of the calc / rollout kernels");
-  }
-  // (dx in the tail of the calc's scratch when the gains' K staging leaves room: on the C5 walk
-  // that takes the rollout's LDS to 52.6 KB, three workgroups per CU; the LDS is allocated in
-  // 2 KB granules (measured: tools/occ_probe.hip), which the occupancy API does not model)
-  D.dxv_mbw = D.mbw_fwd >= (int64_t)D.m * D.n + 2 * D.sN ? 1 : 0;
-  h->fwd_smem = sizeof(double) * (h->pcap + fwd_lds_doubles<kNT, false>(D.sX, D.sN, D.sM) - (D.dxv_mbw ? 2 * D.sN : 0) +
-                                  D.mbw_fwd);
-  h->fwd_mb_variant = -1;  // (re-chosen with the new LDS size)
-  h->ls_slots = 0.;
-  h->calc_smem = sizeof(double) * (h->pcap + 2 * D.sX + D.sM + 5 * (kNT / kWave) + 16 + D.mbw);
-  h->cdiff_smem = sizeof(double) * (h->pcap + D.sX + D.sM);
-  {  // dense-knot fast path: every knot LQR / Euler∘DiffLQR, block LDS-resident
-    bool dense = h->pcap > 0 && d.nx == d.ndx && d.nx <= kNT && d.nu_max <= kNT;
-    for (int t = 0; t <= d.T; ++t)
-      dense = dense && (knots[t].kind == FDDP_KNOT_LQR || knots[t].kind == FDDP_KNOT_EULER_DIFFLQR);
-    h->fused_smem = sizeof(double) * (h->pcap + calc_tiled_lds(D.sX, D.sM));
-    h->fwd_fast_smem = sizeof(double) * (h->pcap + fwd_lds_doubles<kNT, true>(D.sX, D.sN, D.sM));
-    const char* env = std::getenv("FDDP_FAST");
-    const bool off = env && env[0] == '0';
-    h->fast = dense && !off && h->fused_smem <= 160 * 1024 && h->fwd_fast_smem <= 160 * 1024;
-  }
+  plan::LaunchPlan& P = h->plan;
+  P.ov = read_overrides(&P.ov);
+  P.lds = plan::plan_lds(d, knots, params, n_params, P.ov);
+  const plan::LdsPlan& L = P.lds;
+  D.mbw = L.mbw;
+  D.mbw_fwd = L.mbw_fwd;
+  D.mbspill = L.mbspill;
+  D.mbd = L.mbd;
+  // (a re-application of the knots — fddp_set_knots, the MPC loop's circularAppend —
+  // keeps the trial-group size chosen from the last line search's trial counts: resetting it
+  // every step cost the C5 shift protocol's rollout 52.3 -> 65.8 ms)
+  if (!(h->npar_chosen && L.has_mb && !P.ov.ls_par)) D.npar = L.npar;
+  if (L.error) return fail(FDDP_ERR_INVALID_ARG, L.error);
+  D.dxv_mbw = L.dxv_mbw;
   if (n_params > h->params_cap) {  // the old pool stays owned by the handle until fddp_destroy
     double* p = nullptr;
     if ((rc = dalloc(h, &p, n_params))) return rc;
@@ -1003,18 +666,18 @@ int apply_knots(fddp_handle* h, const fddp_knot_desc* knots, const double* param
       const char* name;
     } reqs[] = {
         {ktab::backward_generic_fn(), h->bwd_smem, true, "backward_kernel"},
-        {ktab::forward_fn(ktab::FWD_GENERIC), h->fwd_smem, true, "forward_kernel"},
-        {ktab::forward_fn(ktab::FWD_FAST), h->fwd_fast_smem, true, "forward_kernel<fast>"},
-        {ktab::forward_fn(ktab::FWD_MB), h->fwd_smem, h->has_mb, "forward_kernel<multibody>"},
-        {ktab::forward_fn(ktab::FWD_MB2), h->fwd_smem, h->has_mb, "forward_kernel<multibody, 2 waves/EU>"},
-        {ktab::calc_tiled_fn(), h->fused_smem, true, "calc_tiled_kernel"},
-        {ktab::calc_fn(), h->calc_smem, true, "calc_kernel"},
-        {ktab::calc_diff_fn(), h->cdiff_smem, true, "calc_diff_kernel"},
-        {ktab::mb_knot_fn(ktab::MB_W2), h->mb_diff_smem, h->has_mb, "mb_knot_kernel"},
-        {ktab::mb_knot_fn(ktab::MB_W1), h->mb_diff_smem, h->has_mb, "mb_knot_kernel_w1"},
-        {ktab::mb_knot_fn(ktab::MB_X8), h->mb_diff_smem, h->has_mb, "mb_knot_kernel_x8"},
-        {ktab::mb_knot_fn(ktab::MB_X2), h->mb_diff_smem, h->has_mb, "mb_knot_kernel_x2"},
-        {ktab::mb_knot_fn(ktab::MB_S2), h->mb_diff_smem, h->has_mb, "mb_knot_kernel_s2"},
+        {ktab::forward_fn(ktab::FWD_GENERIC), L.fwd_smem, true, "forward_kernel"},
+        {ktab::forward_fn(ktab::FWD_FAST), L.fwd_fast_smem, true, "forward_kernel<fast>"},
+        {ktab::forward_fn(ktab::FWD_MB), L.fwd_smem, L.has_mb, "forward_kernel<multibody>"},
+        {ktab::forward_fn(ktab::FWD_MB2), L.fwd_smem, L.has_mb, "forward_kernel<multibody, 2 waves/EU>"},
+        {ktab::calc_tiled_fn(), L.fused_smem, true, "calc_tiled_kernel"},
+        {ktab::calc_fn(), L.calc_smem, true, "calc_kernel"},
+        {ktab::calc_diff_fn(), L.cdiff_smem, true, "calc_diff_kernel"},
+        {ktab::mb_knot_fn(ktab::MB_W2), L.mb_diff_smem, L.has_mb, "mb_knot_kernel"},
+        {ktab::mb_knot_fn(ktab::MB_W1), L.mb_diff_smem, L.has_mb, "mb_knot_kernel_w1"},
+        {ktab::mb_knot_fn(ktab::MB_X8), L.mb_diff_smem, L.has_mb, "mb_knot_kernel_x8"},
+        {ktab::mb_knot_fn(ktab::MB_X2), L.mb_diff_smem, L.has_mb, "mb_knot_kernel_x2"},
+        {ktab::mb_knot_fn(ktab::MB_S2), L.mb_diff_smem, L.has_mb, "mb_knot_kernel_s2"},
     };
     for (const Req& r : reqs) {
       if (!r.use) continue;
@@ -1024,50 +687,23 @@ int apply_knots(fddp_handle* h, const fddp_knot_desc* knots, const double* param
                                           std::to_string(r.bytes) + " bytes: " + hipGetErrorString(e));
     }
   }
-  {  // backward sweep variant: MFMA tiles when every running knot has nu == nu_max, or on
-    // multibody horizons (their calcDiff zero-fills the Fu columns beyond a knot's nu, so
-    // the sweep runs a knot on its own nu: the impulse knots of the gaits)
-    bool uniform_nu = d.nu_max > 0;
-    for (int t = 0; t < d.T; ++t) uniform_nu = uniform_nu && knots[t].nu == d.nu_max;
-    uniform_nu = uniform_nu || (h->all_mb && d.nu_max > 0);
-    const char* env = std::getenv("FDDP_BACKWARD");
-    const bool force_generic = env && std::strcmp(env, "generic") == 0;
-    const int ntl = (d.ndx + 15) / 16, mtl = (d.nu_max + 15) / 16;
-    int v = -1;
-    if (uniform_nu && !force_generic) {
-      // eight waves per element, the fastest knot (measured round 4: one wave (C3) or four
-      // (C2) per element are slower, 12.1 / 1.06 ms against 3.6 / 0.89 ms), unless the
-      // four-wave plan keeps more elements resident: the sweep is a serial chain per
-      // element, so its time goes with the rounds of resident workgroups, ceil(B / slots),
-      // and a four-wave knot takes ~1.15x an eight-wave one (C3, B = 512 on 256 CUs: two
-      // four-wave workgroups per CU, one round, 3.20 -> 2.16 ms; C4 and C2 keep eight).
-      // FDDP_BWD_WAVES=1|4|8 overrides.
-      const char* ew = std::getenv("FDDP_BWD_WAVES");
-      int nw = 8;
-      if (ew) nw = ew[0] == '1' ? 1 : (ew[0] == '4' ? 4 : 8);
-      // one-wave plans exist for the small shapes (NTL + MTL <= 4, MTL = 1); four-wave
-      // plans where C^T has its own LDS area (else C^T over Zu needs the 8-wave plan's
-      // late LDS-DMA); everything else runs eight waves (ktab::backward_mfma_setup)
-      const bool known = (ntl == 5 && mtl == 2) || (mtl == 1 && ntl >= 1 && ntl <= 3);
-      if (known) {
-        if (nw == 1 && !(ntl + mtl <= 4 && mtl == 1)) nw = 8;
-        int occ = 0;
-        v = ktab::backward_mfma_setup(ntl, mtl, nw, d.ndx, &occ);
-        if (v < 0 && nw == 4) v = ktab::backward_mfma_setup(ntl, mtl, 8, d.ndx, &occ);
-        if (!ew && v > 0 && mtl == 1) {
-          int cus = 0, occ4 = 0;
-          (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-          const int v4 = ktab::backward_mfma_setup(ntl, mtl, 4, d.ndx, &occ4);
-          if (v4 > 0 && cus > 0 && occ > 0 && occ4 > 0) {
-            const int64_t r8 = (d.B + (int64_t)cus * occ - 1) / ((int64_t)cus * occ);
-            const int64_t r4 = (d.B + (int64_t)cus * occ4 - 1) / ((int64_t)cus * occ4);
-            if (1.2 * (double)r4 < (double)r8) v = v4;
-          }
-        }
-      }
+  plan::DeviceFacts F;  // what plan_variants weighs: queries only, nothing is launched
+  F.cus = h->cus;
+  if (L.has_mb)  // the rollout's residency, for the variants a multibody horizon may take
+    for (int v : {(int)ktab::FWD_GENERIC, (int)ktab::FWD_MB, (int)ktab::FWD_MB2}) {
+      const void* fn = ktab::forward_fn(v);
+      hipFuncAttributes fa{};
+      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&F.fwd_api[v], fn, kNT, L.fwd_smem);
+      (void)hipFuncGetAttributes(&fa, fn);
+      F.fwd_static[v] = (int)fa.sharedSizeBytes;
     }
-    h->bwd_variant = v > 0 ? v : 0;
-  }
+  if (L.uniform_nu && !P.ov.bwd_generic)  // the MFMA sweep's plans (each sets its own dynamic LDS)
+    for (int nw : {1, 4, 8})
+      F.bwd_code[plan::bwd_slot(nw)] = ktab::backward_mfma_setup(L.ntl, L.mtl, nw, d.ndx, &F.bwd_occ[plan::bwd_slot(nw)]);
+  P.var = plan::plan_variants(L, d, P.ov, F);
+  if (L.npar_adapt && !L.fast && std::getenv("FDDP_STAMPS"))  // (diagnostic runs: the rollout's residency)
+    std::fprintf(stderr, "[fddp] rollout: %.0f workgroups on %d CUs (LDS %zu B per workgroup)\n", P.var.ls_slots, F.cus,
+                 L.fwd_smem);
   return FDDP_OK;
 }
 
@@ -1113,6 +749,7 @@ int fddp_create(const fddp_dims* dims, const fddp_knot_desc* knots, const double
   auto* h = new fddp_handle_s();
   h->dims = d;
   h->device = device;
+  h->cus = prop.multiProcessorCount;
   fddp_default_params(&h->prm);
   int rc;
   auto bail = [&](int code) {
@@ -1140,7 +777,7 @@ int fddp_create(const fddp_dims* dims, const fddp_knot_desc* knots, const double
   // rollouts for the elements that backtrack (CROCODDYL_AMD_LS_PAR = 1 is serial)
   D.npar = 1;
   D.ls_order = nullptr;
-  if (const char* e = std::getenv("CROCODDYL_AMD_LS_PAR")) D.npar = h->npar_env = std::max(1, std::min(16, std::atoi(e)));
+  h->plan.ov = read_overrides(nullptr);
   const int64_t B = d.B, K1 = (int64_t)d.T + 1, K0 = d.T;
   {  // SolverBoxFDDP's qp_(nu, 100, 0.1, 1e-5, 0.) (box-fddp.cpp:16); unused until BOXFDDP
     fddp_boxqp_params bp;
@@ -1214,8 +851,8 @@ void fddp_destroy(fddp_handle* h) {
     std::vector<unsigned long long> v((size_t)h->dims.B * 140);
     if (hipMemcpy(v.data(), h->D.stamps, v.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
       const char* names[8] = {"p1_G", "p1_H", "p1_inv", "b1_dma", "p2_K", "p2_Vupd", "b2_p3", "b3_wait"};
-      std::fprintf(stderr, "[fddp stamps] mean cycles per element (variant %d):\n", h->bwd_variant);
-      for (int w = 0; w < h->bwd_variant % 10; ++w) {
+      std::fprintf(stderr, "[fddp stamps] mean cycles per element (variant %d):\n", h->plan.var.bwd);
+      for (int w = 0; w < h->plan.var.bwd % 10; ++w) {
         std::fprintf(stderr, "  wave %d:", w);
         for (int ph = 0; ph < 8; ++ph) {
           double s2 = 0;
@@ -1224,10 +861,10 @@ void fddp_destroy(fddp_handle* h) {
         }
         std::fprintf(stderr, "\n");
       }
-      if (h->has_mb || h->fast) {
+      if (h->plan.lds.has_mb || h->plan.lds.fast) {
         const char* mn[5] = {"state", "params", "gains", "calc", "stores_checks"};
         std::fprintf(stderr, "[fddp stamps] %s rollout, wave 0's mean cycles per element (all trials):",
-                     h->fast ? "dense fast-path" : "multibody");
+                     h->plan.lds.fast ? "dense fast-path" : "multibody");
         for (int ph = 0; ph < 5; ++ph) {
           double s2 = 0;
           for (int b = 0; b < h->dims.B; ++b) s2 += (double)v[(size_t)h->dims.B * 128 + (size_t)b * 8 + ph];
@@ -1278,7 +915,7 @@ void fddp_destroy(fddp_handle* h) {
                        "CU over the launch (%.3f ms)\n",
                        n, cus.size(), most, area / ((double)(t1 - t0) * (double)cus.size()), (t1 - t0) * 1e-5);
       }
-      if (h->fast) {
+      if (h->plan.lds.fast) {
         const char* fn[8] = {"stage", "compute", "-", "-", "-", "blocks", "-", "-"};
         std::fprintf(stderr, "[fddp stamps] fused calc/calcDiff, mean cycles per element:\n");
         for (int w = 0; w < 8; ++w) {
@@ -1307,7 +944,7 @@ void fddp_destroy(fddp_handle* h) {
 int fddp_set_model_params(fddp_handle* h, const double* params, int64_t n_params) {
   if (!h || !params || n_params != h->n_params) return fail(FDDP_ERR_INVALID_ARG, "fddp_set_model_params: size");
   DeviceGuard g(h->device);
-  if (h->has_mb) {  // variable-size multibody blocks: re-validate and re-plan the LDS
+  if (h->plan.lds.has_mb) {  // variable-size multibody blocks: re-validate and re-plan the LDS
     int rc;
     if ((rc = check_knots(h->dims, h->knots.data(), params, n_params, "fddp_set_model_params", false))) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1488,12 +1125,12 @@ int fddp_solve(fddp_handle* h, int maxiter, int is_feasible, double reg_init, fd
 int fddp_get_kernel_info(fddp_handle* h, int32_t out[8]) {
   if (!h || !out) return fail(FDDP_ERR_INVALID_ARG, "fddp_get_kernel_info: null argument");
   DeviceGuard g(h->device);
-  out[0] = h->has_mb && !h->fast ? mb_variant(h) : -1;
-  out[1] = h->fast ? (int)ktab::FWD_FAST : rollout_variant(h);
-  out[2] = h->bwd_variant;
+  out[0] = h->plan.var.mb;
+  out[1] = h->plan.var.fwd;
+  out[2] = h->plan.var.bwd;
   out[3] = h->D.mbspill;
-  out[4] = (int32_t)h->mb_diff_smem;
-  out[5] = (int32_t)(h->fast ? h->fwd_fast_smem : h->fwd_smem);
+  out[4] = (int32_t)h->plan.lds.mb_diff_smem;
+  out[5] = (int32_t)(h->plan.lds.fast ? h->plan.lds.fwd_fast_smem : h->plan.lds.fwd_smem);
   out[6] = h->D.npar;
   out[7] = 0;
   return FDDP_OK;

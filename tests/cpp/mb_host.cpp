@@ -19,6 +19,8 @@ static int g_dump_shape[12][2];
     g_dump_shape[slot][1] = c_;                                              \
   } while (0)
 #include "../../crocoddyl_amd/csrc/multibody.hpp"
+// the library's dispatch rules (plain host functions: no HIP runtime call)
+#include "../../crocoddyl_amd/csrc/launch_plan.hpp"
 
 using namespace fddp::mb;
 
@@ -59,7 +61,7 @@ void mb_host_calc_diff(const double* P, int nx, int m, const double* x, const do
 }
 
 // The same under caller-supplied plan flags: a handle takes its flags from the maxima over
-// all its knots (fddp_hip.hip apply_knots), so a knot can run a plan its own shape would
+// all its knots (launch_plan.hpp plan_lds), so a knot can run a plan its own shape would
 // not pick (a flight knot under the flags of the contact knots beside it).
 void mb_host_calc_diff_flags(const double* P, int nx, int m, int spill, const double* x, const double* u, int use_u,
                              double* Fx, double* Fu, double* Lxx, double* Lxu, double* Luu, double* Lx, double* Lu,
@@ -121,16 +123,43 @@ int mb_host_plan(const double* P, int m, int64_t* lds_bytes) {
 }
 
 extern "C" {
-// The multibody rollout's dynamic LDS per workgroup for a block (fddp_hip.hip apply_knots):
-// the staged parameter block, the trial's vectors (x, u, next x, the sums, the flag; dx in
-// the knot calc's scratch) and the dense knot calc's scratch (calc_dense_doubles, also in
-// *dense); in *work the tree calc's scratch (calc_work_doubles), for comparison.
-int64_t mb_host_rollout_lds(const double* P, int nx, int nu_max, int64_t* dense, int64_t* work) {
-  const Blk b = parse(P);
-  const int64_t sX = fddp::pad2(nx), sM = fddp::pad2(nu_max);
-  *dense = fddp::pad2(calc_dense_doubles(b.nj, b.nc));
-  *work = fddp::pad2(calc_work_doubles(b.nj, b.nc));
-  return 8 * (fddp::pad2((int64_t)P[3]) + 2 * sX + sM + 5 * 4 + 8 + 2 + *dense);
+// The launch plan libfddp_hip gives a handle of these knots under overrides `ov` on a device
+// of facts `facts` (launch_plan.hpp plan_lds, plan_variants: the rules the library runs).
+// out: the LdsPlan's and the VariantPlan's fields in the order below (tests/variant_cases.py
+// PLAN_FIELDS). Returns 0, or 1 with the plan's refusal in msg.
+int mb_host_launch_plan(const fddp_dims* d, const fddp_knot_desc* knots, const double* params, int64_t n_params,
+                        const fddp::plan::Overrides* ov, const fddp::plan::DeviceFacts* facts, double* out, char* msg,
+                        int cap) {
+  const fddp::plan::LdsPlan l = fddp::plan::plan_lds(*d, knots, params, n_params, *ov);
+  if (l.error) return std::snprintf(msg, cap, "%s", l.error), 1;
+  const fddp::plan::VariantPlan v = fddp::plan::plan_variants(l, *d, *ov, *facts);
+  const double f[] = {(double)l.has_mb,       (double)l.all_mb,     (double)l.mb_nj,      (double)l.mbw,
+                      (double)l.mbw_fwd,      (double)l.mbd,        (double)l.mbspill,    (double)l.dxv_mbw,
+                      (double)l.mb_all_lds,   (double)l.mb_diff_smem, (double)l.pcap,     (double)l.fwd_smem,
+                      (double)l.calc_smem,    (double)l.cdiff_smem, (double)l.fused_smem, (double)l.fwd_fast_smem,
+                      (double)l.fast,         (double)l.npar,       (double)l.npar_adapt, (double)l.uniform_nu,
+                      (double)l.ntl,          (double)l.mtl,        (double)v.mb,         (double)v.fwd,
+                      (double)v.bwd,          v.ls_slots};
+  for (int i = 0; i < (int)(sizeof(f) / sizeof(f[0])); ++i) out[i] = f[i];
+  return 0;
+}
+
+// Workgroups per CU of a kernel under the 2 KB LDS granule (launch_plan.hpp resident_per_cu)
+int mb_host_resident_per_cu(int api, int64_t dyn_bytes, int64_t static_bytes) {
+  return fddp::plan::resident_per_cu(api, (size_t)dyn_bytes, (size_t)static_bytes);
+}
+
+// The multibody rollout's dynamic LDS per workgroup on a horizon of one block of knot kind
+// `kind` and `nu` controls (the plan's fwd_smem; -1: refused); the dense knot calc's scratch
+// in *dense (Dev::mbw_fwd), the tree calc's in *work (Dev::mbw), for comparison.
+int64_t mb_host_rollout_lds(const double* P, int kind, int nu, int nx, int nu_max, int64_t* dense, int64_t* work) {
+  const fddp_dims d = {nx, 2 * parse(P).nj, nu_max, 1, 1};
+  const fddp_knot_desc kd = {kind, nu, 0, 0};
+  const fddp_knot_desc knots[2] = {kd, kd};
+  const fddp::plan::LdsPlan l = fddp::plan::plan_lds(d, knots, P, (int64_t)P[3], fddp::plan::Overrides());
+  *dense = l.mbw_fwd;
+  *work = l.mbw;
+  return l.error ? -1 : (int64_t)l.fwd_smem;
 }
 }
 

@@ -192,16 +192,16 @@ def test_talos_rollout_fits_three_workgroups_per_cu(lib, talos_walk):  # noqa: F
     import ctypes as C
     g, models = talos_walk
     lib.mb_host_rollout_lds.restype = C.c_int64
-    lib.mb_host_rollout_lds.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_int64),
-                                        C.POINTER(C.c_int64)]
+    lib.mb_host_rollout_lds.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     nu_max = max(m.nu for m in models)
     worst = 0
     for model in models:
         kind, nu, blk = model.pack()
         blk = np.ascontiguousarray(blk[0])
         dense, work = C.c_int64(0), C.c_int64(0)
-        lds = lib.mb_host_rollout_lds(_p(blk), model.state.nx, nu_max, C.byref(dense), C.byref(work))
-        assert dense.value < work.value, (dense.value, work.value)
+        lds = lib.mb_host_rollout_lds(_p(blk), kind, nu, model.state.nx, nu_max, C.byref(dense), C.byref(work))
+        assert lds > 0 and dense.value < work.value, (lds, dense.value, work.value)
         worst = max(worst, lds)
     granule = 2048
     assert 3 * (-(-(worst + 256) // granule) * granule) <= 160 * 1024, worst

@@ -21,8 +21,8 @@ D = C.POINTER(C.c_double)
 
 @pytest.fixture(scope="module")
 def lib():
-    hdr = os.path.join(ROOT, "crocoddyl_amd", "csrc", "multibody.hpp")
-    if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(os.path.getmtime(SRC), os.path.getmtime(hdr)):
+    hdrs = [os.path.join(ROOT, "crocoddyl_amd", "csrc", h) for h in ("multibody.hpp", "launch_plan.hpp")]
+    if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(map(os.path.getmtime, [SRC] + hdrs)):
         os.makedirs(os.path.dirname(OUT), exist_ok=True)
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O2", "-std=c++17",
                                "-shared", "-fPIC", "-o", OUT, SRC])

@@ -1,10 +1,15 @@
 """The size ladder of tests/test_kernel_variants_gpu.py: problems on seeded trees whose
 multibody calcDiff plans sit next to the thresholds of libfddp_hip's kernel dispatch
-(fddp_hip.hip apply_knots / mb_variant): the 128-thread kernel's nj <= 16 and 40 KB,
-the spilled plan's nj >= 21 and 80 KB, the parallel line-search trials' nj >= 24.
-Shared with tests/test_variant_ladder_host.py, which pins every rung's side of every
-threshold on the CPU (so a layout change that moves a rung fails there, not by a GPU
-test quietly running another kernel)."""
+(crocoddyl_amd/csrc/launch_plan.hpp plan_lds / plan_variants): the 128-thread kernel's
+nj <= 16 and 40 KB, the spilled plan's nj >= 21 and 80 KB, the parallel line-search trials'
+nj >= 24. Shared with tests/test_variant_ladder_host.py, which pins every rung's side of
+every threshold on the CPU (so a layout change that moves a rung fails there, not by a GPU
+test quietly running another kernel). launch_plan / handle_plan evaluate that header
+itself, through the host harness (tests/cpp/mb_host.cpp mb_host_launch_plan)."""
+import ctypes as C
+
+import numpy as np
+
 from crocoddyl_amd import _abi, multibody as mb, synthetic
 from crocoddyl_amd.problem import pack_problem
 
@@ -64,33 +69,58 @@ def setup(x0s, running, terminal):
     return dict(dims=dims, knots=knots, pool=pool, x0s=x0s, running=running, terminal=terminal)
 
 
-def handle_plan(lib, running, terminal):
-    """The multibody calcDiff plan libfddp_hip gives a handle of these knots (fddp_hip.hip
-    apply_knots), from the host build of the device code (tests/cpp/mb_host.cpp): nj, the
-    all-LDS plan's bytes, the handle's spill flags (from the maxima over the knots' shapes)
-    and the bytes of the plan under them, and each knot's own flags."""
-    import ctypes as C
 
-    import numpy as np
-    lib.mb_host_plan_under.restype = C.c_int64
-    lib.mb_host_plan_under.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_int64, C.POINTER(C.c_int64)]
-    lib.mb_host_spill_flags.argtypes = [C.c_int] * 6 + [C.c_int64, C.c_int]
-    lib.mb_host_plan.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int64)]
+
+# ---- the launch plan (crocoddyl_amd/csrc/launch_plan.hpp) through the host harness ----
+class Overrides(C.Structure):
+    """launch_plan.hpp Overrides; the defaults are the variables left unset."""
+    _fields_ = [(f, C.c_int) for f in ("mb_w1", "mb_nt", "mb_spill", "fwd_mb_off", "fwd_mbw", "bwd_waves",
+                                       "bwd_generic", "fast_off", "ls_par")]
+
+    def __init__(self, **kw):
+        super().__init__(**{**dict(mb_w1=-1, mb_spill=-1), **kw})
+
+
+class DeviceFacts(C.Structure):
+    """launch_plan.hpp DeviceFacts: fwd_* by FWD_* variant, bwd_* for 1 / 4 / 8 waves."""
+    _fields_ = [("cus", C.c_int), ("fwd_api", C.c_int * 4), ("fwd_static", C.c_int * 4), ("bwd_code", C.c_int * 3),
+                ("bwd_occ", C.c_int * 3)]
+
+
+# mb_host_launch_plan's out[] (tests/cpp/mb_host.cpp)
+PLAN_FIELDS = ("has_mb", "all_mb", "mb_nj", "mbw", "mbw_fwd", "mbd", "mbspill", "dxv_mbw", "mb_all_lds", "mb_diff_smem",
+               "pcap", "fwd_smem", "calc_smem", "cdiff_smem", "fused_smem", "fwd_fast_smem", "fast", "npar", "npar_adapt",
+               "uniform_nu", "ntl", "mtl", "mb", "fwd", "bwd", "ls_slots")
+
+
+def launch_plan(lib, dims, knots, pool, overrides=None, facts=None):
+    """The launch plan libfddp_hip gives a handle of (dims, knots, pool) under `overrides` on
+    a device of `facts`, evaluated by the library's own rules (launch_plan.hpp plan_lds,
+    plan_variants) in the host harness: a dict of PLAN_FIELDS. A refusal raises ValueError."""
+    kd = (_abi.KnotDesc * len(knots))(*[_abi.KnotDesc(*k) for k in knots])
+    pool = np.ascontiguousarray(pool, dtype=np.float64)
+    out = (C.c_double * len(PLAN_FIELDS))()
+    msg = C.create_string_buffer(256)
+    lib.mb_host_launch_plan.restype = C.c_int
+    lib.mb_host_launch_plan.argtypes = [C.POINTER(_abi.Dims), C.POINTER(_abi.KnotDesc), _abi.D, C.c_int64,
+                                        C.POINTER(Overrides), C.POINTER(DeviceFacts), _abi.D, C.c_char_p, C.c_int]
+    if lib.mb_host_launch_plan(C.byref(dims), kd, _abi.dptr(pool), pool.size, C.byref(overrides or Overrides()),
+                               C.byref(facts or DeviceFacts()), out, msg, len(msg)):
+        raise ValueError(msg.value.decode())
+    return {f: int(v) for f, v in zip(PLAN_FIELDS, out)}
+
+
+def handle_plan(lib, running, terminal, B=1, overrides=None, facts=None):
+    """The multibody calcDiff plan libfddp_hip gives a handle of these knots: nj, the
+    all-LDS plan's bytes, the handle's spill flags and the bytes of the plan under them, the
+    calcDiff variant (mb) and the rest of launch_plan's dict; and each knot's own flags
+    (own_flags, tests/cpp/mb_host.cpp mb_host_plan)."""
+    knots, pool = pack_problem(running, terminal, B)
+    st = running[0].state
     m = max(r.nu for r in running)
-    models = list(dict.fromkeys(list(running) + [terminal]))
-    blks = [np.ascontiguousarray(em.pack()[2][0]) for em in models]
-    ptr = [b.ctypes.data_as(C.POINTER(C.c_double)) for b in blks]
-    shape = (C.c_int64 * 7)()
-    shapes = []
-    for p in ptr:
-        lib.mb_host_plan_under(p, 0, 0, shape)
-        shapes.append(list(shape))
-    mx = [max(s[i] for s in shapes) for i in range(7)]
-    pmax = mx[6]
-    all_lds = max(lib.mb_host_plan_under(p, 0, pmax, shape) for p in ptr)
-    flags = lib.mb_host_spill_flags(*mx[:6], pmax, m) if all_lds > 80 * KB else 0
+    p = launch_plan(lib, _abi.Dims(st.nx, st.ndx, m, len(running), B), knots, pool, overrides, facts)
+    lib.mb_host_plan.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int64)]
     lds = C.c_int64(0)
-    own = [lib.mb_host_plan(p, m, C.byref(lds)) for p in ptr]
-    own_of = dict(zip(map(id, models), own))
-    return dict(nj=mx[0], all_lds=all_lds, flags=flags, bytes=max(lib.mb_host_plan_under(p, flags, pmax, shape) for p in ptr),
-                own_flags=[own_of[id(em)] for em in list(running) + [terminal]], nc=[s[2] for s in shapes])
+    own = [lib.mb_host_plan(_abi.dptr(np.ascontiguousarray(em.pack()[2][0])), m, C.byref(lds))
+           for em in list(running) + [terminal] if em.pack()[0] >= _abi.KNOT_EULER_FREEFWD]
+    return dict(p, nj=p["mb_nj"], all_lds=p["mb_all_lds"], flags=p["mbspill"], bytes=p["mb_diff_smem"], own_flags=own)
