@@ -667,10 +667,12 @@ int apply_knots(fddp_handle* h, const fddp_knot_desc* knots, const double* param
     } reqs[] = {
         {ktab::backward_generic_fn(), h->bwd_smem, true, "backward_kernel"},
         {ktab::forward_fn(ktab::FWD_GENERIC), L.fwd_smem, true, "forward_kernel"},
-        {ktab::forward_fn(ktab::FWD_FAST), L.fwd_fast_smem, true, "forward_kernel<fast>"},
+        // (the fast path's two kernels only where it is taken: plan_lds drops it when their
+        // LDS would exceed the CU's, which must not refuse the handle; dense (78, 32))
+        {ktab::forward_fn(ktab::FWD_FAST), L.fwd_fast_smem, L.fast, "forward_kernel<fast>"},
         {ktab::forward_fn(ktab::FWD_MB), L.fwd_smem, L.has_mb, "forward_kernel<multibody>"},
         {ktab::forward_fn(ktab::FWD_MB2), L.fwd_smem, L.has_mb, "forward_kernel<multibody, 2 waves/EU>"},
-        {ktab::calc_tiled_fn(), L.fused_smem, true, "calc_tiled_kernel"},
+        {ktab::calc_tiled_fn(), L.fused_smem, L.fast, "calc_tiled_kernel"},
         {ktab::calc_fn(), L.calc_smem, true, "calc_kernel"},
         {ktab::calc_diff_fn(), L.cdiff_smem, true, "calc_diff_kernel"},
         {ktab::mb_knot_fn(ktab::MB_W2), L.mb_diff_smem, L.has_mb, "mb_knot_kernel"},

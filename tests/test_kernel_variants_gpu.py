@@ -59,14 +59,14 @@ _live = helpers.live
 _REF = {}  # (problem key, xreg) -> (oracle phases, floors or None): shared by the cases of one problem
 
 
-def _oracle_phases(key, S, xs, us, xreg, floors, alphas=ALPHAS):
-    k = (key, repr(xreg), alphas)
+def _oracle_phases(key, S, xs, us, xreg, floors, alphas=ALPHAS, feasible=False):
+    k = (key, repr(xreg), alphas, feasible)
     if k not in _REF:
         d = S["dims"]
 
         def run(pool):
             o = oracle_lib.Oracle(d, S["knots"], pool, S["x0s"], threads=4)
-            return _live(S, helpers.phases(o, xs, us, alphas, xreg, helpers.ALL_BLOCKS))
+            return _live(S, helpers.phases(o, xs, us, alphas, xreg, helpers.ALL_BLOCKS, feasible))
 
         ro = run(S["pool"])
         fl = None
@@ -86,11 +86,13 @@ def _handle(S, want):
     return g, info
 
 
-def _check_phases(key, S, xs, us, g, floors=False, xregs=(NAN, 1e-9), alphas=ALPHAS):
+def _check_phases(key, S, xs, us, g, floors=False, xregs=(NAN, 1e-9), alphas=ALPHAS, feasible=False):
+    """feasible: what set_candidate is told of (xs, us) (the gaps count as closed: the feas
+    arms of the sweep's Vx and of the expected-improvement sums)."""
     g.set_debug(True)  # Vxx / Vx / Q* are stored in debug mode
     for xreg in xregs:
-        ro, fl = _oracle_phases(key, S, xs, us, xreg, floors, alphas)
-        rg = _live(S, helpers.phases(g, xs, us, alphas, xreg, helpers.ALL_BLOCKS))
+        ro, fl = _oracle_phases(key, S, xs, us, xreg, floors, alphas, feasible)
+        rg = _live(S, helpers.phases(g, xs, us, alphas, xreg, helpers.ALL_BLOCKS, feasible))
         np.testing.assert_array_equal(rg["bwd_status"], ro["bwd_status"])
         for a in alphas:
             np.testing.assert_array_equal(rg[f"fwd_status@{a}"], ro[f"fwd_status@{a}"])
@@ -101,7 +103,7 @@ def _check_phases(key, S, xs, us, g, floors=False, xregs=(NAN, 1e-9), alphas=ALP
             if "@" in q:  # the trial of a failed rollout (status 1 on both sides) is not an output
                 ok = ro["fwd_status@" + q.split("@")[1]] == 0
                 a, b = a[ok], b[ok]
-            helpers.parity(f"{key} xreg={xreg} {q}", a, b, TOL, fl[q] if fl else None)
+            helpers.parity(f"{key}{' feasible' if feasible else ''} xreg={xreg} {q}", a, b, TOL, fl[q] if fl else None)
 
 
 def _check_solve(key, S, xs0, us0, g, maxiter, floors=False):
@@ -273,7 +275,7 @@ def _sweep_code(nx, waves):
 
 
 def _lqr(nx, nu, T=6, B=3):
-    key = f"lqr{nx}x{nu}"
+    key = f"lqr{nx}x{nu}" + ("" if T == 6 else f"T{T}")
     if key not in _PROBLEMS:
         rng = np.random.default_rng(nx * 100 + nu)
         model = synthetic.lqr_models(nx, nu, B, rng, drift_free=False)  # ActionModelLQR(nx, nu, False), seeded per element
@@ -321,7 +323,10 @@ def test_ladder_rung_matches_the_oracle(rung):
     x0s, running, terminal = vc.build(rung)
     S = vc.setup(x0s, running, terminal)
     d = S["dims"]
-    g, info = _handle(S, dict(mb=r["mb"], mbspill=r["flags"], npar=r["npar"], fwd=_abi.FWD_MB2))
+    want = dict(mb=r["mb"], mbspill=r["flags"], npar=r["npar"], fwd=_abi.FWD_MB2)
+    if "bwd" in r:  # the rungs that are there for a Riccati sweep variant too
+        want["bwd"] = r["bwd"]
+    g, info = _handle(S, want)
     assert info["mb_diff_smem"] <= 80 * vc.KB and (info["mb_diff_smem"] <= 40 * vc.KB) == r["lds40"], info
     xs, us = _moving_candidate(S, 3, q=0.1, v=0.3)
     _check_phases(rung, S, xs, us, g)

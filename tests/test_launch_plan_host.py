@@ -118,6 +118,22 @@ def test_sweep_rule_two_control_tiles_keep_eight_waves(lib):  # noqa: F811
     assert _sweep(lib, 65, [17] * 2, 9, _sweep_facts(5, 2, occ4=5, occ8=4), bwd_waves=1)["bwd"] == 528
 
 
+def test_fast_path_gives_way_at_the_lds_limit(lib):  # noqa: F811
+    """The largest dense shapes of the 5 x 2 sweep: (77, 32) still fits the fused calc's LDS,
+    (78, 32) does not (164,000 B) and plans the generic knot kernels, which fit; the sweep
+    stays 528 (fddp_create once refused the second: it asked for the fused kernel's LDS
+    whether or not the plan took it). (80, 32): the block no longer fits the knot kernels'
+    LDS either and is read from global memory."""
+    f = _sweep_facts(5, 2, occ4=1, occ8=1)
+    p = _sweep(lib, 77, [32] * 2, 3, f)
+    assert p["fast"] and p["fused_smem"] <= 160 * KB and p["fwd"] == _abi.FWD_FAST and p["bwd"] == 528, p
+    p = _sweep(lib, 78, [32] * 2, 3, f)
+    assert not p["fast"] and p["fused_smem"] > 160 * KB and p["fwd"] == _abi.FWD_GENERIC and p["bwd"] == 528, p
+    assert p["pcap"] > 0 and max(p["fwd_smem"], p["calc_smem"], p["cdiff_smem"]) <= 160 * KB, p
+    p = _sweep(lib, 80, [32] * 2, 3, vc.sweep_facts_of_the_device(5, 2, 80))
+    assert not p["fast"] and p["pcap"] == 0 and p["fwd"] == _abi.FWD_GENERIC and p["bwd"] == 0, p
+
+
 def test_sweep_generic(lib):  # noqa: F811
     f = _sweep_facts(1, 1, occ4=5, occ8=4)
     assert _sweep(lib, 16, [2, 2], 3, f)["bwd"] == 118

@@ -15,20 +15,23 @@ from crocoddyl_amd.problem import pack_problem
 
 pytestmark = pytest.mark.gpu
 
+CASES = [(-1000.0, 1.5, 1e9), (-1000.0, 1.5, 1e2), (-50.0, 10.0, 1e9)]  # Luu = l I, regfactor, regmax
 
-@pytest.mark.parametrize("variant", ["default", "generic"])
-@pytest.mark.parametrize("luu,regfactor,regmax", [(-1000.0, 1.5, 1e9), (-1000.0, 1.5, 1e2), (-50.0, 10.0, 1e9)])
-def test_retries_to_regmax_as_the_oracle(variant, luu, regfactor, regmax, monkeypatch):
-    monkeypatch.delenv("FDDP_BACKWARD", raising=False)
-    if variant == "generic":
-        monkeypatch.setenv("FDDP_BACKWARD", "generic")
-    nx, nu, T, B = 24, 12, 10, 2
+
+def negative_luu_pair(nx, nu, T, luu, regfactor, regmax, bwd=None):
+    """(gpu handle, oracle) of the LQR horizon ActionModelLQR(nx, nu, False) with Luu = luu
+    (a scalar: luu I; or a (B, nu, nu) array, one matrix per element), B = 2, under
+    (regfactor, regmax), both at the default candidate. bwd: the sweep code the handle must
+    report (kernel_info) before anything runs."""
+    B = 2
     model = ActionModelLQR(nx, nu, False)
-    model.Luu = luu * np.eye(nu)
+    model.Luu = luu * np.eye(nu) if np.ndim(luu) == 0 else np.asarray(luu, float)
     knots, pool = pack_problem([model] * T, model, B)
     dims = _abi.Dims(nx, nx, nu, T, B)
     x0s = np.stack([np.linspace(-1, 1, nx), np.linspace(1, -1, nx)])
     g = helpers.Gpu(dims, knots, pool, x0s)
+    if bwd is not None:
+        assert g.kernel_info()["bwd"] == bwd, g.kernel_info()
     o = oracle_lib.Oracle(dims, knots, pool, x0s)
     prm = oracle_lib.default_params()
     prm.regfactor = regfactor
@@ -37,13 +40,32 @@ def test_retries_to_regmax_as_the_oracle(variant, luu, regfactor, regmax, monkey
     o.set_params(prm)
     for h in (g, o):
         h.set_candidate(None, None, False)
+    return g, o
+
+
+def solve_as_the_oracle(g, o, luu, regfactor, regmax):
+    """solve(maxiter=3, reg_init=1e-9) on both: status, counts, regularisation and step
+    length equal, xs within 1e-8; and what the case is there for, on the oracle. Returns
+    the oracle's results."""
     rg = helpers.results_dict(g.solve(maxiter=3, reg_init=1e-9))
     ro = helpers.results_dict(o.solve(maxiter=3, reg_init=1e-9))
     for f in ("status", "iter", "n_iter_run", "xreg", "ureg", "steplength", "is_feasible"):
         np.testing.assert_array_equal(rg[f], ro[f], err_msg=f)
-    if regmax == 1e9 and regfactor == 1.5:
+    scalar = np.ndim(luu) == 0  # (per-element Luu: the caller says what its elements are there for)
+    if scalar and regmax == 1e9 and regfactor == 1.5:
         # more increases than the old fixed cap of 64: 1e-9 * 1.5^64 = 1.8e2 < |Luu|
         assert (ro["xreg"] > 1e-9 * 1.5 ** 64).all() and (ro["status"] != _abi.STATUS_REGMAX).all()
-    if regmax == 1e2:
+    if scalar and regmax == 1e2:
         assert (ro["status"] == _abi.STATUS_REGMAX).all()
     helpers.parity("xs", g.xs(), o.xs(), 1e-8)
+    return ro
+
+
+@pytest.mark.parametrize("variant", ["default", "generic"])
+@pytest.mark.parametrize("luu,regfactor,regmax", CASES)
+def test_retries_to_regmax_as_the_oracle(variant, luu, regfactor, regmax, monkeypatch):
+    monkeypatch.delenv("FDDP_BACKWARD", raising=False)
+    if variant == "generic":
+        monkeypatch.setenv("FDDP_BACKWARD", "generic")
+    g, o = negative_luu_pair(24, 12, 10, luu, regfactor, regmax)
+    solve_as_the_oracle(g, o, luu, regfactor, regmax)

@@ -44,6 +44,12 @@ def test_rung_is_on_its_side_of_every_threshold(lib, rung):  # noqa: F811
     assert p["npar"] == r["npar"], p
     # the variant launch_plan.hpp plan_variants derives from these
     assert p["mb"] == r["mb"], p
+    if "bwd" in r:  # the sweep: on the codes a device offers these tiles (its n <= 78 rule for 5 x 2 included)
+        st = running[0].state
+        assert (p["ntl"], p["mtl"]) == (5, 2) and p["uniform_nu"] and p["all_mb"], p
+        assert 65 <= st.ndx <= 78 and 17 <= max(m.nu for m in running) <= 32, p
+        facts = vc.sweep_facts_of_the_device(p["ntl"], p["mtl"], st.ndx)
+        assert vc.handle_plan(lib, running, terminal, facts=facts)["bwd"] == r["bwd"], p
 
 
 def test_rungs_hug_their_edges(lib):  # noqa: F811

@@ -32,6 +32,14 @@ RUNGS = {
     # contact / free / contact / free knots of the n = 22 tree, contact terminal: the free
     # knots (own flags 3) run under the handle's flags 7
     "mixed22": dict(kind="mixed", n=22, contacts=TIP, x2_nj=False, lds40=False, flags=7, npar=4, mb=_abi.MB_S2),
+    # trees whose (ndx, nu) = (2 n + 12, n) reach the 5 x 2-tile MFMA Riccati sweep (code 528:
+    # ndx 65..78, nu 17..32) away from the Talos shape (76, 32): (66, 27), (70, 29), (74, 31).
+    # bwd: the sweep code (asserted where present)
+    "float27": dict(kind="floating", n=27, contacts=(), x2_nj=False, lds40=False, flags=3, npar=4, mb=_abi.MB_S2, bwd=528),
+    "float27c": dict(kind="floating", n=27, contacts=TIP, x2_nj=False, lds40=False, flags=7, npar=4, mb=_abi.MB_S2, bwd=528),
+    "float29c": dict(kind="floating", n=29, contacts=TIP, x2_nj=False, lds40=False, flags=7, npar=4, mb=_abi.MB_S2, bwd=528),
+    "float31": dict(kind="floating", n=31, contacts=(), x2_nj=False, lds40=False, flags=3, npar=4, mb=_abi.MB_S2, bwd=528),
+    "float31c": dict(kind="floating", n=31, contacts=TIP, x2_nj=False, lds40=False, flags=7, npar=4, mb=_abi.MB_S2, bwd=528),
     # fixed-base trees on either side of the nj <= 16 rule, both under 40 KB
     "arm16": dict(kind="arm", n=16, contacts=(), x2_nj=True, lds40=True, flags=0, npar=1, mb=_abi.MB_X2),
     "arm17": dict(kind="arm", n=17, contacts=(), x2_nj=False, lds40=True, flags=0, npar=1, mb=_abi.MB_W2),
@@ -50,6 +58,18 @@ def build(name):
     x0s, run_c, term_c = synthetic.build_floating(T=T, B=B, robot=robot, contacts=list(r["contacts"]))
     _, run_f, _ = synthetic.build_floating(T=T, B=B, robot=robot)
     return x0s, [run_c[0], run_f[0], run_c[0], run_f[0]], term_c
+
+
+def sweep_facts_of_the_device(ntl, mtl, ndx):
+    """The sweep codes a device offers a handle of (ntl x mtl) tiles, as k_bwd.hip setup_one
+    answers: -1 (no such plan) where ndx exceeds the plan's Z column stride 16 ntl - 2; the
+    5 x 2 plan exists with eight waves only, the (1..3) x 1 plans with one, four and eight."""
+    f = DeviceFacts(cus=1)
+    for i, w in enumerate((1, 4, 8)):
+        have = (mtl == 1 and 1 <= ntl <= 3) or ((ntl, mtl, w) == (5, 2, 8))
+        f.bwd_code[i] = (ntl * 10 + mtl) * 10 + w if have and ndx <= 16 * ntl - 2 else -1
+        f.bwd_occ[i] = 1
+    return f
 
 
 def mixed_arm(T, B, seed=0):
