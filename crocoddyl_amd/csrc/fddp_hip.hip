@@ -340,16 +340,27 @@ int launch_cost_sum(fddp_handle* h, int sel, double* out) {
   LAUNCH_CHECK();
   return FDDP_OK;
 }
+// The dense knots' calcDiff and the gaps of every knot (calc_diff_kernel, one workgroup per
+// element), after the multibody knots' kernel. On an all-multibody horizon that pass has
+// no calcDiff work: the gaps alone, one wave per (knot, element).
+int launch_dense_diff_gaps(fddp_handle* h, int sel, int gaps) {
+  const Dev& D = h->D;
+  if (!h->plan.lds.all_mb) {
+    KLAUNCH(ktab::calc_diff(dim3(D.B), h->plan.lds.cdiff_smem, h->stream, D, sel, gaps, h->plan.lds.pcap));
+  } else if (gaps) {
+    hipLaunchKernelGGL(gaps_kernel, dim3(D.T + 1, D.B), dim3(kWave), 0, h->stream, D, sel);
+    LAUNCH_CHECK();
+  }
+  return FDDP_OK;
+}
 int launch_calc_diff(fddp_handle* h, int sel, int gaps) {
   if (h->plan.lds.fast) return launch_fused(h, -1, sel, gaps);
   Timed tm(h, 1);
-  const Dev& D = h->D;
   if (h->plan.lds.has_mb) {  // multibody knots: one workgroup per knot, before the gaps pass
     int rc;
     if ((rc = launch_mb(h, -1, sel))) return rc;
   }
-  KLAUNCH(ktab::calc_diff(dim3(D.B), h->plan.lds.cdiff_smem, h->stream, D, sel, gaps, h->plan.lds.pcap));
-  return FDDP_OK;
+  return launch_dense_diff_gaps(h, sel, gaps);
 }
 // problem.calc (sel_calc) + cost_ = sum of knot costs, then problem.calcDiff
 // (sel_diff, + gaps): one fused pass on the fast path.
@@ -367,8 +378,7 @@ int launch_calc_then_diff(fddp_handle* h, int sel_calc, int sel_calc_sum, int se
     if ((rc = launch_mb(h, sel_calc, sel_diff))) return rc;
     if (!h->plan.lds.all_mb) KLAUNCH(ktab::calc(dim3(D.B), h->plan.lds.calc_smem, h->stream, D, sel_calc, h->plan.lds.pcap, 1));
     if ((rc = launch_cost_sum(h, sel_calc_sum, nullptr))) return rc;
-    KLAUNCH(ktab::calc_diff(dim3(D.B), h->plan.lds.cdiff_smem, h->stream, D, sel_diff, gaps, h->plan.lds.pcap));
-    return FDDP_OK;
+    return launch_dense_diff_gaps(h, sel_diff, gaps);
   }
   if ((rc = launch_calc(h, sel_calc))) return rc;
   if ((rc = launch_cost_sum(h, sel_calc_sum, nullptr))) return rc;

@@ -257,12 +257,34 @@ __global__ __launch_bounds__(NT) void calc_diff_kernel(Dev D, int sel, int gaps,
   }
 }
 
+// The gap computation of SolverDDP::calcDiff (ddp.cpp:160-176) alone, for horizons whose
+// knots are all multibody kinds (calc_diff_kernel has no calcDiff work there and would
+// only walk each element's knots one after another, staging every parameter block, to
+// form the gaps). One wave per (knot t = blockIdx.x, element b = blockIdx.y), nothing
+// staged: fs[0] = diff(xs[0], x0), fs[t] = diff(xs[t], data[t-1].xnext). Same selection,
+// flags and difference as calc_diff_kernel's gaps branch, so fs is the same bits.
+#if defined(FDDP_TU_MAIN)
+__global__ __launch_bounds__(kWave) void gaps_kernel(Dev D, int sel) {
+  const int t = blockIdx.x, b = blockIdx.y;
+  const ElemState s = D.st[b];
+  if (!selected(s, sel)) return;
+  double* f = D.fs + D.knot(b, t) * D.sN;
+  if (!s.is_feasible) {
+    const double* x1 = t == 0 ? D.x0 + (int64_t)b * D.sX : D.xnext[s.cur] + D.run(b, t - 1) * D.sX;
+    state_diff_wg<kWave>(D, D.xs[s.cur] + D.knot(b, t) * D.sX, x1, f);
+  } else if (!s.was_feasible) {  // closing the gaps
+    for (int i = threadIdx.x; i < D.n; i += kWave) f[i] = 0.;
+  }
+}
+#endif
+
 // Multibody knots (multibody.hpp), knot-parallel: one mb::kMbDiffNT-thread workgroup per
 // (knot t = blockIdx.x, element b = blockIdx.y); knots of other kinds return.
 // calc (xnext, knot cost) for elements selected by sel_calc and calcDiff
 // (derivative blocks) for those selected by sel_diff (-1: none), fused: the
 // calcDiff evaluates the dynamics the calc needs anyway. The gaps of these
-// knots are written by calc_diff_kernel as for any knot.
+// knots are written after it: by gaps_kernel on an all-multibody horizon, by
+// calc_diff_kernel beside the dense knots' calcDiff on a mixed one.
 template <int NT, int SP = 0>
 __device__ __forceinline__ void mb_knot_body(const Dev& D, int sel_calc, int sel_diff) {
   const int t = blockIdx.x, b = blockIdx.y;

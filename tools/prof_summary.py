@@ -35,6 +35,7 @@ CLASSES = {  # bench.py's rooflines keys -> kernel name fragments
     "forward": ("forward_kernel",),
     "mb_calc_diff": ("mb_knot_kernel",),
     "calc_fused": ("calc_tiled_kernel", "calc_diff_kernel"),  # the dense knots' calc / calcDiff
+    "gaps": ("gaps_kernel",),  # the gaps of all-multibody horizons
 }
 
 

@@ -16,7 +16,7 @@ import statistics
 import sys
 
 CLASSES = {
-    "calcDiff": ("mb_knot_kernel", "calc_diff_kernel", "calc_tiled_kernel", "cost_sum_kernel"),
+    "calcDiff": ("mb_knot_kernel", "calc_diff_kernel", "gaps_kernel", "calc_tiled_kernel", "cost_sum_kernel"),
     "backward": ("backward_mfma_kernel", "backward_kernel"),
     "forward": ("forward_kernel", "ls_select_kernel"),
 }
