@@ -333,7 +333,19 @@ int fddp_stopping_criteria(fddp_handle* h, double* stop);
  * iter_==0 calc in SolverDDP::calcDiff, ddp.cpp:158), xreg_/ureg_ (NaN on a
  * fresh solver, solver-base.cpp:19-20) and was_feasible_. */
 int fddp_set_solver_state(fddp_handle* h, int iter, double xreg, double ureg, int was_feasible);
-/* xs_try/us_try of the last tryStep. */
+/* xs_try/us_try of the last tryStep / forwardPass, or what the last line search of a
+ * solve left in the trial buffer.
+ *  - A rollout stopped by a forward_error wrote the knots up to and including the failing
+ *    one; the knots after it keep what earlier rollouts left there, as the reference's
+ *    xs_try_ / us_try_ do. After a search that accepted nothing every knot holds the last
+ *    trial that reached it, whatever the trial-group size.
+ *  - The dense fast path (kernel info fwd == FAST) does not stop at the failing knot: it
+ *    rolls the whole horizon out and applies the checks afterwards. The status is the
+ *    reference's, but the knots past the failing one hold the blown-up rollout's values
+ *    (inf / NaN among them), and the cost_try a failed fddp_forward_pass returns is the
+ *    whole horizon's sum, not the partial sum the reference stopped at.
+ *  - After an accepted trial the trial buffer holds the previous candidate (acceptance
+ *    flips the two buffers); the reference's xs_try_ then equals its new xs_. */
 int fddp_get_xs_try(fddp_handle* h, double* out);
 int fddp_get_us_try(fddp_handle* h, double* out);
 

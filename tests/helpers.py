@@ -327,5 +327,22 @@ def parity(name, a, b, tol, floor=None, scale_floor=1e-3):
     return e
 
 
+def parity_worst(name, items, tol):
+    """Several parity checks at the bar `tol` recorded as one: items are (a, b), each compared
+    as parity() compares it alone (its own component scales); the item with the largest
+    elem_err is the one asserted and logged, so every item meets the bar. A NaN elem_err (NaN
+    or inf in an output, a shape mismatch) is the largest of all."""
+    assert items, name
+    worst = None
+    for a, b in items:
+        e = elem_err(a, b)
+        if e != e:  # NaN: nothing is worse, and nothing may replace it
+            worst = (e, a, b)
+            break
+        if worst is None or e > worst[0]:
+            worst = (e, a, b)
+    return parity(f"{name} (worst of {len(items)})", worst[1], worst[2], tol)
+
+
 def results_dict(r):
     return {f: np.array([getattr(x, f) for x in r]) for f, _ in _abi.Result._fields_}

@@ -107,8 +107,8 @@ def _check_phases(key, S, xs, us, g, floors=False, xregs=(NAN, 1e-9), alphas=ALP
 
 
 def _check_solve(key, S, xs0, us0, g, maxiter, floors=False):
-    """solve(maxiter) from (xs0, us0) vs the oracle: status / iter / n_iter_run / steplength
-    equal, xs / us / cost element-wise."""
+    """solve(maxiter) from (xs0, us0) vs the oracle: status / iter / n_iter_run / steplength /
+    xreg / ureg / is_feasible equal, xs / us / cost element-wise."""
     d = S["dims"]
     k = (key, "solve", maxiter)
     if k not in _REF:
@@ -124,7 +124,7 @@ def _check_solve(key, S, xs0, us0, g, maxiter, floors=False):
     (xo, uo, co, ro), fl = _REF[k]
     g.set_candidate(xs0, us0, False)
     rg = helpers.results_dict(g.solve(maxiter=maxiter, reg_init=1e-9))
-    for f in ("status", "iter", "n_iter_run", "steplength"):
+    for f in ("status", "iter", "n_iter_run", "steplength", "xreg", "ureg", "is_feasible"):
         np.testing.assert_array_equal(rg[f], ro[f], err_msg=f)
     helpers.parity(f"{key} solve{maxiter} xs", g.xs(), xo, TOL, fl[0])
     helpers.parity(f"{key} solve{maxiter} us", _live(S, {"us": g.us()})["us"], uo, TOL, fl[1])
