@@ -122,6 +122,23 @@ struct MfmaCfg {
   static constexpr int LDV = NP + 2;
   static constexpr int LDQ = MP;
   static_assert(MP <= 64, "u block must fit one wave for the factorisation");
+  // Z column stride ZLD = NP - 2 (= 2 mod 4): the 16 lanes of a B fragment
+  // read 16 columns at a stride of 2*ZLD = 4 (mod 8) banks, conflict-free
+  // (a stride of NP was an 8-way conflict). k-steps past ZLD read the next
+  // column's first rows (or the 2 zero doubles after the last column); they
+  // only ever multiply the zero rows of Vxx' / G, so nothing changes.
+  static constexpr int ZLD = NP - 2;
+  // C^T, the transposed inverse Cholesky factor (chol_inv_sweep), at the odd leading
+  // dimension LDT (its fragment reads step along it: conflict-free), in an area of its own
+  // where that fits the 160 KB beside everything else (ct_own). Where it does not (the
+  // 5 x 2-tile shape), there is no copy: C itself (Qi) gets the odd leading dimension
+  // LDC = MP + 1, under which the K product's second pass and k read C^T's fragments
+  // straight out of C as conflict-free as its first pass reads C's
+  static constexpr int LDT = MP + 1;
+  static constexpr int VEC0 = LDV * NP + LDV * MP + 2 * LDQ * MP + 4 * NP + 2 * MP + (2 * MP > 64 ? 2 * MP : 64);
+  static constexpr int Z0 = (NP + MP) * ZLD + 2;
+  static constexpr bool ct_own = sizeof(double) * (((VEC0 + 40 + 5) & ~1) + Z0 + MP * LDT) <= 160 * 1024;
+  static constexpr int LDC = ct_own ? LDQ : MP + 1;
   // LDS carve (doubles). Z = [Fx | Fu] is stored with the compile-time
   // column stride NP (zero rows/cols beyond n, m) so that every fragment
   // address is a per-lane base plus an immediate offset.
@@ -129,7 +146,7 @@ struct MfmaCfg {
   static constexpr int oQxu = oV + LDV * NP;
   static constexpr int oQuu = oQxu + LDV * MP;
   static constexpr int oQi = oQuu + LDQ * MP;
-  static constexpr int oVx = oQi + LDQ * MP;
+  static constexpr int oVx = oQi + LDC * MP;
   static constexpr int oQx = oVx + NP;
   static constexpr int oLx = oQx + NP;
   static constexpr int oFs = oLx + NP;
@@ -137,24 +154,16 @@ struct MfmaCfg {
   static constexpr int oLu = oQu + MP;
   static constexpr int oKv = oLu + MP;  // kv + quuk: the sweep's 64-double row buffer (wave 0, P1)
   static constexpr int oQuuk = oKv + MP;
-  static constexpr int oRed = oKv + (2 * MP > 64 ? 2 * MP : 64);  // 5 sums x up to 8 waves
-  static constexpr int oFlag = oRed + 40;  // flag; Quu-ready, G-done, P2-done, H-done counters (5 ints)
-  // Z column stride ZLD = NP - 2 (= 2 mod 4): the 16 lanes of a B fragment
-  // read 16 columns at a stride of 2*ZLD = 4 (mod 8) banks, conflict-free
-  // (a stride of NP was an 8-way conflict). k-steps past ZLD read the next
-  // column's first rows (or the 2 zero doubles after the last column); they
-  // only ever multiply the zero rows of Vxx' / G, so nothing changes.
-  static constexpr int ZLD = NP - 2;
+  static constexpr int oRed = oKv + (2 * MP > 64 ? 2 * MP : 64);
+  // the sums' buffer. ct_own: 5 sums x up to 8 waves (wg_sums at the sweep's end). Else the
+  // per-knot sums, one slot per wave that has a term (BwdPlan::red_slot: wave 0's three, two
+  // per x-block owner), and the terminal knot's two sums x 8 waves
+  static constexpr int RED = ct_own ? 40 : (3 + 2 * NTL > 16 ? 3 + 2 * NTL : 16);
+  static constexpr int oFlag = oRed + RED;  // flag; Quu-ready, G-done, P2-done counters (5 ints, one spare)
   static constexpr int oZx = (oFlag + 4 + 1) & ~1;
   static constexpr int oZu = oZx + NP * ZLD;
   static constexpr int total0 = oZu + MP * ZLD + 2;
-  // C^T, the transposed inverse Cholesky factor (chol_inv_sweep), at the odd leading
-  // dimension LDT (its fragment reads step along it: conflict-free): its own area when
-  // it fits the 160 KB, else over Zu, which is dead from the H tiles of a knot until
-  // the next knot's LDS-DMA (issued after B2 by the 8-wave plan, see bwd_knot)
-  static constexpr int LDT = MP + 1;
-  static constexpr bool ct_own = sizeof(double) * (total0 + MP * LDT) <= 160 * 1024;
-  static constexpr int oCt = ct_own ? total0 : oZu;
+  static constexpr int oCt = total0;  // (ct_own only)
   // the prefetch plan's second operand buffers (BwdPlan::prefetch; C^T in its own area):
   // Z, then lx, lu, fs
   static constexpr int oZx2 = (total0 + MP * LDT + 1) & ~1;
@@ -168,8 +177,24 @@ struct MfmaCfg {
   static constexpr int oCb = (oFs2 + NP + 1) & ~1;
   static constexpr bool pre_fits = ct_own && sizeof(double) * (oCb + 2 * CB) <= 160 * 1024;
   static constexpr int total = pre_fits ? oCb + 2 * CB : (ct_own ? total0 + MP * LDT : total0);
-  static_assert(ct_own || MP * LDT <= MP * ZLD, "C^T over Zu");
   static constexpr size_t bytes = sizeof(double) * total;
+  // the carve: every area starts where the one before it ends (so no two overlap), the
+  // LDS-DMA targets are 16-byte aligned, and what a plan without the prefetch buffers
+  // carves fits the CU's 160 KB
+  static_assert(oQxu - oV == LDV * NP && oQuu - oQxu == LDV * MP && oQi - oQuu == LDQ * MP &&
+                    oVx - oQi >= (MP - 1) * LDC + MP && oQx - oVx == NP && oLx - oQx == NP && oFs - oLx == NP &&
+                    oQu - oFs == NP && oLu - oQu == MP && oKv - oLu == MP && oQuuk - oKv == MP &&
+                    oRed - oKv >= 2 * MP && oRed - oKv >= 64 && oFlag - oRed == RED,
+                "LDS carve: the matrix, vector and sum areas in order, none over another");
+  static_assert(sizeof(double) * (oZx - oFlag) >= 5 * sizeof(int) && oZu - oZx == NP * ZLD &&
+                    total0 - oZu == MP * ZLD + 2 && (!ct_own || oCt >= total0),
+                "LDS carve: the counters, Z and C^T");
+  static_assert(oZx % 2 == 0 && oZu % 2 == 0 && oLx % 2 == 0 && oLu % 2 == 0 && oFs % 2 == 0 && LDV % 2 == 0 &&
+                    ZLD % 2 == 0,
+                "LDS-DMA targets are 16-byte aligned");
+  static_assert(ct_own ? (LDC == LDQ && sizeof(double) * (total0 + MP * LDT) <= 160 * 1024)
+                       : (LDC % 2 == 1 && sizeof(double) * total0 <= 160 * 1024),
+                "C^T in its own area, or read out of C at an odd leading dimension; within 160 KB");
 };
 
 
@@ -262,8 +287,9 @@ __device__ __forceinline__ bool sym_sweep_inverse(const double* Quu, double* Qi,
 // LLT solves than the solves from each other (the round-4 parity trace: K 3e-8 vs
 // 1.5e-10), the two triangular products as close as the solves. A pivot <= 0 is the
 // LLT failure. C: lower triangular, zero above the diagonal and beyond m.
-// Cx (may be null): C's transpose as well, C(i, j) at Cx[i * LDQ + j]; Ct null: no C^T.
-template <int MP, int LDQ, int LDT>
+// Cx (may be null): C's transpose as well, C(i, j) at Cx[i * LDC + j]; Ct null: no C^T.
+// Quu has the leading dimension LDQ, C (and Cx) LDC.
+template <int MP, int LDQ, int LDT, int LDC = LDQ>
 __device__ __forceinline__ bool chol_inv_sweep(const double* Quu, double* C, double* Ct, double* rb, int m, int lane,
                                                int* ct_ready, int ct_target, double* Cx = nullptr) {
   constexpr int RPL = MP * MP / 64;
@@ -303,7 +329,7 @@ __device__ __forceinline__ bool chol_inv_sweep(const double* Quu, double* C, dou
     }
   }
   // 1 / sqrt(d_i) by the diagonal's lanes (one each), published; C(i, j) = L^-1(i, j) / sqrt(d_i)
-  // into C (column-major, ld LDQ) and C^T (column-major, ld LDT)
+  // into C (column-major, ld LDC) and C^T (column-major, ld LDT)
   asm volatile("" ::: "memory");
 #pragma unroll
   for (int r = 0; r < RPL; ++r)
@@ -319,9 +345,9 @@ __device__ __forceinline__ bool chol_inv_sweep(const double* Quu, double* C, dou
     const double s = rb[i];
     double v = 0.;
     if (i < m && jc < m) v = i == jc ? s : (jc < i ? A[r] * s : 0.);
-    C[jc * LDQ + i] = v;
+    C[jc * LDC + i] = v;
     if (Ct) Ct[i * LDT + jc] = v;
-    if (Cx) Cx[i * LDQ + jc] = v;
+    if (Cx) Cx[i * LDC + jc] = v;
   }
   return bad;
 }
@@ -334,21 +360,20 @@ __device__ __forceinline__ bool chol_inv_sweep(const double* Quu, double* C, dou
 //   C22 = chol_inv(S);    C21 = -C22 (L21 C11)
 // (the blocked right-looking Cholesky, the off-diagonal products on MFMA in registers:
 // the accumulator register s of G / T is the A and B fragment of k-step s). C as
-// chol_inv_sweep's (col-major, ld LDQ, zero above the diagonal and beyond m), then C^T
-// (ld LDT) once the other waves are done with its area.
-template <int LDQ, int LDT>
-__device__ __forceinline__ bool chol_inv_blocked2(const double* Quu, double* C, double* Ct, double* rb, int m, int lane,
-                                                  int* ct_ready, int ct_target) {
+// chol_inv_sweep's (col-major, ld LDC, zero above the diagonal and beyond m; Quu has ld
+// LDQ), then its transposed copy C^T (ld LDT) where the caller keeps one (Ct not null).
+template <int LDQ, int LDT, int LDC = LDQ>
+__device__ __forceinline__ bool chol_inv_blocked2(const double* Quu, double* C, double* Ct, double* rb, int m, int lane) {
   const int q = lane >> 4, c = lane & 15;
   const int m1 = m < 16 ? m : 16, m2 = m - 16;
   // C11, and its transpose in the lower-left block (free until C21 lands there)
-  bool bad = chol_inv_sweep<16, LDQ, LDT>(Quu, C, nullptr, rb, m1, lane, nullptr, 0, C + 16);
+  bool bad = chol_inv_sweep<16, LDQ, LDT, LDC>(Quu, C, nullptr, rb, m1, lane, nullptr, 0, C + 16);
   asm volatile("" ::: "memory");
   if (m2 > 0) {
     f64x4 G = {0., 0., 0., 0.}, T = {0., 0., 0., 0.}, S, X = {0., 0., 0., 0.};
     // G = C11 A12: A(c, 4s+q) = C11(c, 4s+q); B(4s+q, c) = A12(4s+q, c) = Quu(16+c, 4s+q)
 #pragma unroll
-    for (int s = 0; s < 4; ++s) G = mfma4(C[(4 * s + q) * LDQ + c], Quu[(4 * s + q) * LDQ + 16 + c], G);
+    for (int s = 0; s < 4; ++s) G = mfma4(C[(4 * s + q) * LDC + c], Quu[(4 * s + q) * LDQ + 16 + c], G);
     // S = A22 - G^T G, held as S(q+4r, c); staged (by symmetry) at (c, 16+q+4r), the
     // upper-right block (zero in C, rewritten below)
 #pragma unroll
@@ -356,39 +381,38 @@ __device__ __forceinline__ bool chol_inv_blocked2(const double* Quu, double* C, 
 #pragma unroll
     for (int s = 0; s < 4; ++s) S = mfma4(-G[s], G[s], S);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) C[(16 + q + 4 * r) * LDQ + c] = S[r];
+    for (int r = 0; r < 4; ++r) C[(16 + q + 4 * r) * LDC + c] = S[r];
     // T = L21 C11: A(c, 4s+q) = L21(c, 4s+q) = G(4s+q, c); B(4s+q, c) = C11(4s+q, c),
     // stored transposed at (16+c, 4s+q)
 #pragma unroll
-    for (int s = 0; s < 4; ++s) T = mfma4(G[s], C[(4 * s + q) * LDQ + 16 + c], T);
+    for (int s = 0; s < 4; ++s) T = mfma4(G[s], C[(4 * s + q) * LDC + 16 + c], T);
     asm volatile("" ::: "memory");
-    bad = chol_inv_sweep<16, LDQ, LDT>(C + 16 * LDQ, C + 16 * LDQ + 16, nullptr, rb, m2, lane, nullptr, 0) || bad;
+    bad = chol_inv_sweep<16, LDC, LDT, LDC>(C + 16 * LDC, C + 16 * LDC + 16, nullptr, rb, m2, lane, nullptr, 0) || bad;
     asm volatile("" ::: "memory");
     // C21 = -C22 T: A(c, 4s+q) = C22(c, 4s+q) at (16+c, 16+4s+q); B = T's register s
 #pragma unroll
-    for (int s = 0; s < 4; ++s) X = mfma4(-C[(16 + 4 * s + q) * LDQ + 16 + c], T[s], X);
+    for (int s = 0; s < 4; ++s) X = mfma4(-C[(16 + 4 * s + q) * LDC + 16 + c], T[s], X);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      C[c * LDQ + 16 + q + 4 * r] = X[r];
-      C[(16 + q + 4 * r) * LDQ + c] = 0.;  // the staging of S
+      C[c * LDC + 16 + q + 4 * r] = X[r];
+      C[(16 + q + 4 * r) * LDC + c] = 0.;  // the staging of S
     }
   } else {
 #pragma unroll
     for (int r = 0; r < 8; ++r) {  // rows 16..31 (C11^T's block too), then the upper-right block
       const int e = lane + 64 * r, i = 16 + (e & 15), j = e >> 4;
-      C[j * LDQ + i] = 0.;
+      C[j * LDC + i] = 0.;
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) C[(16 + q + 4 * r) * LDQ + c] = 0.;
+    for (int r = 0; r < 4; ++r) C[(16 + q + 4 * r) * LDC + c] = 0.;
   }
   asm volatile("" ::: "memory");
-  if (ct_target > 0) {
-    lds_wait_ge(ct_ready, ct_target);
-  }
+  if (Ct) {
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int e = lane + 64 * r, i = e & 31, j = e >> 5;
-    Ct[i * LDT + j] = C[j * LDQ + i];
+    for (int r = 0; r < 16; ++r) {
+      const int e = lane + 64 * r, i = e & 31, j = e >> 5;
+      Ct[i * LDT + j] = C[j * LDC + i];
+    }
   }
   return bad;
 }
@@ -470,8 +494,8 @@ __device__ __forceinline__ bool sym_sweep_inverse_blk(const double* Quu, double*
 // The masked / relabelled inverse an InvMap describes (the box QP's free
 // Hessian, box_qp.hpp) with the register sweep: the masked matrix is staged
 // into Qi, swept in place (the sweep reads all of it before writing), and
-// the result is cut to the `out` set.
-template <int MP, int LDQ>
+// the result is cut to the `out` set. H has the leading dimension LDH, Qi LDQ.
+template <int MP, int LDH, int LDQ = LDH>
 __device__ __forceinline__ bool sym_sweep_inverse_masked(const double* H, double* Qi, double* rb, int m, int lane,
                                                          const InvMap& mp) {
   // staged four entries per lane at a time, loads before stores (one LDS round trip per four)
@@ -479,13 +503,13 @@ __device__ __forceinline__ bool sym_sweep_inverse_masked(const double* H, double
   for (; e + 3 * 64 < m * m; e += 4 * 64) {
     double v[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = mp.load(H, LDQ, (e + 64 * q) % m, (e + 64 * q) / m);
+    for (int q = 0; q < 4; ++q) v[q] = mp.load(H, LDH, (e + 64 * q) % m, (e + 64 * q) / m);
 #pragma unroll
     for (int q = 0; q < 4; ++q) Qi[((e + 64 * q) / m) * LDQ + (e + 64 * q) % m] = v[q];
   }
   for (; e < m * m; e += 64) {
     const int i = e % m, j = e / m;
-    Qi[j * LDQ + i] = mp.load(H, LDQ, i, j);
+    Qi[j * LDQ + i] = mp.load(H, LDH, i, j);
   }
   const bool bad = sym_sweep_inverse<MP, LDQ>(Qi, Qi, rb, m, lane);
   asm volatile("" ::: "memory");
@@ -532,8 +556,9 @@ struct BwdPlan {
   int dmarank[8];
   int xwaves;  // waves owning x blocks (the P3 consumers)
   bool prefetch;  // double-buffered operands, DMA at the knot's start (see below)
+  int rslot[5][8];  // red_slot(j, w), tabulated
   constexpr BwdPlan()
-      : nown{}, blk{}, ntile{}, tile{}, uwaves(0), gwaves(0), ndma(0), dmarank{}, xwaves(0), prefetch(false) {
+      : nown{}, blk{}, ntile{}, tile{}, uwaves(0), gwaves(0), ndma(0), dmarank{}, xwaves(0), prefetch(false), rslot{} {
     int owner[16] = {};
     if (NW == 1) {  // small knots: one wave owns every block (no partial barrier ever waits)
       for (int u = 0; u < MTL; ++u) blk[0][nown[0]++] = NTL + u;
@@ -615,9 +640,13 @@ struct BwdPlan {
         if (nown[w] == 0) dmarank[w] = ndma++;
     } else if (NW <= 4) {
       for (int w = 0; w < NW; ++w) dmarank[w] = ndma++;
-    } else {  // the waves without x blocks: no MFMA work in P2 / P3
-      for (int w = 0; w < NW; ++w)
+    } else {
+      // the waves with neither x blocks (no MFMA work in P2 / P3) nor the inversion: the DMA
+      // goes right after B1, where wave 0 has k and Quu k to form, which the x-block owners
+      // wait for at B2 (a DMA instruction holds its wave for some 400 cycles)
+      for (int w = 1; w < NW; ++w)
         if (!owns_x(w)) dmarank[w] = ndma++;
+      if (ndma == 0) dmarank[0] = ndma++;
     }
     for (int w = 0; w < NW; ++w) xwaves += owns_x(w) ? 1 : 0;
     // V tiles: the diagonal with its owner, the rest greedily
@@ -637,6 +666,8 @@ struct BwdPlan {
         ++ntile[w];
         vload[w] += 1;
       }
+    for (int j = 0; j < 5; ++j)
+      for (int w = 0; w < 8; ++w) rslot[j][w] = w < NW ? red_slot(j, w) : -1;
   }
   constexpr bool owns_x(int w) const {
     for (int o = 0; o < nown[w]; ++o)
@@ -647,6 +678,17 @@ struct BwdPlan {
     for (int o = 0; o < nown[w]; ++o)
       if (blk[w][o] >= NTL) return true;
     return false;
+  }
+  // Where wave w's sum j of a knot's five (Qu.k, k.Quu k, Vx.fs, fs.Vxx fs, Qu.Qu) goes in
+  // the per-knot sums' buffer, or -1 where the wave has no such term (its sum is an exact
+  // +0, which changes no total): wave 0 forms the three u sums, the x-block owners the two fs
+  // sums. At most 3 + 2 NTL slots; the owners in wave order, which is the order they are added in.
+  constexpr int red_slot(int j, int w) const {
+    if (j == 0 || j == 1 || j == 4) return w == 0 ? (j == 4 ? 2 : j) : -1;
+    if (!owns_x(w)) return -1;
+    int r = 0;
+    for (int v = 0; v < w; ++v) r += owns_x(v) ? 1 : 0;
+    return 3 + 2 * r + (j - 2);
   }
   constexpr int slot(int w, int blockid) const {  // index o of blockid in blk[w], or -1
     for (int o = 0; o < nown[w]; ++o)
@@ -676,11 +718,11 @@ struct BwdLds {
 
 // SolverBoxFDDP::computeGains on wave 0 (box-fddp.cpp:48-79): the box QP
 // (box_qp.hpp) on Quu, Qu with bounds u_lb - us, u_ub - us, warm-started at
-// the previous k; leaves Quu_inv in Qi, k = -x in kv (and in D.k), and Qu
+// the previous k; leaves Quu_inv in Qi (leading dimension LDC), k = -x in kv (and in D.k), and Qu
 // zeroed on the clamped set. Returns false where the reference raises
 // backward_error (including its qp_ size check: the QP has
 // runningModels[0]->nu variables, box-fddp.cpp:16, box-qp.cpp:53-72).
-template <int MP, int LDQ>
+template <int MP, int LDQ, int LDC>
 __device__ __forceinline__ bool box_gains_wave(const Dev& D, const BwdLds& L, int b, int t, int cur, int lane) {
   const int nu = D.knots[t].nu;
   if (nu != D.knots[0].nu) return false;
@@ -699,9 +741,9 @@ __device__ __forceinline__ bool box_gains_wave(const Dev& D, const BwdLds& L, in
   int ninv = 0;
   auto inv = [&](const InvMap& mp) {
     ++ninv;
-    return sym_sweep_inverse_masked<MP, LDQ>(L.Quu, L.Qi, L.rowbuf, nu, lane, mp);
+    return sym_sweep_inverse_masked<MP, LDQ, LDC>(L.Quu, L.Qi, L.rowbuf, nu, lane, mp);
   };
-  const bool qp_ok = box_qp_wave(L.Quu, LDQ, L.Qi, LDQ, L.rowbuf, nu, lane, q, lb, ub, x, D.boxcfg, inv, true, fsol,
+  const bool qp_ok = box_qp_wave(L.Quu, LDQ, L.Qi, LDC, L.rowbuf, nu, lane, q, lb, ub, x, D.boxcfg, inv, true, fsol,
                                  finv, iters);
   if (D.box_stats && lane == 0) {
     atomicAdd(D.box_stats, 1ull);
@@ -716,7 +758,7 @@ __device__ __forceinline__ bool box_gains_wave(const Dev& D, const BwdLds& L, in
     if (!((fsol >> lane) & 1)) L.qu[lane] = 0.;
   }
   if (D.dQuuInv)
-    for (int e = lane; e < nu * nu; e += 64) D.dQuuInv[rr * D.sMM + (e / nu) * D.m + e % nu] = L.Qi[(e / nu) * LDQ + e % nu];
+    for (int e = lane; e < nu * nu; e += 64) D.dQuuInv[rr * D.sMM + (e / nu) * D.m + e % nu] = L.Qi[(e / nu) * LDC + e % nu];
   return true;
 }
 
@@ -726,7 +768,7 @@ template <int NTL, int MTL, int NW, int W>
 __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, int t, bool feas, double xreg,
                                          double ureg, int cur, Stamp& stamp, double (&red5)[5]) {
   using Cfg = MfmaCfg<NTL, MTL>;
-  constexpr int NP = Cfg::NP, MP = Cfg::MP, JT = Cfg::JT, LDV = Cfg::LDV, LDQ = Cfg::LDQ, ZLD = Cfg::ZLD;
+  constexpr int NP = Cfg::NP, MP = Cfg::MP, JT = Cfg::JT, LDV = Cfg::LDV, LDQ = Cfg::LDQ, LDC = Cfg::LDC, ZLD = Cfg::ZLD;
   constexpr BwdPlan<NTL, MTL, NW> P{};
   constexpr int NO = P.nown[W];
   constexpr int NA = NO > 0 ? NO : 1;
@@ -758,13 +800,7 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
   const double* const lxv = odd ? L.lxv2 : L.lxv;
   const double* const luv = odd ? L.luv2 : L.luv;
   const double* const fsb = odd ? L.fsb2 : L.fsb;
-  // part 1: Fx (the Zx buffer: no reader after P1) by the DMA waves other than 0, so it can
-  // go right after B1 even where C^T lives over Zu; part 2: the rest (Fu into Zu, Lx, Lu and
-  // the prefetch plan's blocks); 3: everything
-  constexpr int NDX = P.ndma - (P.dmarank[0] >= 0 ? 1 : 0);
-  constexpr int CTC = (MP * Cfg::LDT + ZLD - 1) / ZLD;  // Zu columns C^T covers (when it lies over Zu)
-  constexpr int RKX = P.dmarank[W] - (P.dmarank[0] >= 0 && P.dmarank[W] > P.dmarank[0] ? 1 : 0);
-  auto issue_dma = [&](int part) {
+  auto issue_dma = [&]() {
   if constexpr (P.dmarank[W] >= 0) {
     if (t > 0) {  // operands of knot t-1 (prefetch plan: into the other buffers, with fs)
       constexpr int ND = P.ndma, RK = P.dmarank[W];
@@ -773,34 +809,12 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
       double* const nZx = nb ? L.Zx2 : L.Zx;
       double* const nZu = nb ? L.Zu2 : L.Zu;
       const bool full = (n & 1) == 0 && ZLD - n <= 2 * 64;
-      if (part == 3) {
-        if (full) {
-          dma_cols_full<ND, ZLD>(nZx, D.Fx + k1 * D.sNN, n, n, D.zero16, RK, lane);
-        } else {
-          dma_cols<ND>(nZx, ZLD, D.Fx + k1 * D.sNN, n, n, RK, lane);
-        }
-      } else if (part == 1) {
-        // (and the columns of Fu past the ones C^T lies over: CTC Zu columns hold C^T)
-        if constexpr (W != 0 && NDX > 0) {
-          const int c0 = CTC < m ? CTC : m;
-          if (full) {
-            dma_cols_full<NDX, ZLD>(nZx, D.Fx + k1 * D.sNN, n, n, D.zero16, RKX, lane);
-            if (c0 < m)
-              dma_cols_full<NDX, ZLD>(nZu + c0 * ZLD, D.Fu + k1 * D.sNM + (int64_t)c0 * n, n, m - c0, D.zero16, RKX,
-                                      lane);
-          } else {
-            dma_cols<NDX>(nZx, ZLD, D.Fx + k1 * D.sNN, n, n, RKX, lane);
-            if (c0 < m) dma_cols<NDX>(nZu + c0 * ZLD, ZLD, D.Fu + k1 * D.sNM + (int64_t)c0 * n, n, m - c0, RKX, lane);
-          }
-        }
-        return;
-      }
-      // part 2 of a split: only the Fu columns under C^T
-      const int mu2 = part == 2 ? (CTC < m ? CTC : m) : m;
       if (full) {
-        dma_cols_full<ND, ZLD>(nZu, D.Fu + k1 * D.sNM, n, mu2, D.zero16, RK, lane);
+        dma_cols_full<ND, ZLD>(nZx, D.Fx + k1 * D.sNN, n, n, D.zero16, RK, lane);
+        dma_cols_full<ND, ZLD>(nZu, D.Fu + k1 * D.sNM, n, m, D.zero16, RK, lane);
       } else {
-        dma_cols<ND>(nZu, ZLD, D.Fu + k1 * D.sNM, n, mu2, RK, lane);
+        dma_cols<ND>(nZx, ZLD, D.Fx + k1 * D.sNN, n, n, RK, lane);
+        dma_cols<ND>(nZu, ZLD, D.Fu + k1 * D.sNM, n, m, RK, lane);
       }
       dma_vec<ND>(nb ? L.lxv2 : L.lxv, D.Lx + k1 * D.sN, n, RK, lane);
       dma_vec<ND>(nb ? L.luv2 : L.luv, D.Lu + k1 * D.sM, m, RK, lane);
@@ -814,7 +828,7 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
     }
   }
   };
-  if constexpr (pre) issue_dma(3);
+  if constexpr (pre) issue_dma();
   double* V = L.V;
   double* Qxu = L.Qxu;
   double* Quu = L.Quu;
@@ -1021,9 +1035,6 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
     if (lane == 0) lds_signal(L.flag + 1);
     __builtin_amdgcn_s_setprio(0);
   }
-  if constexpr (!Cfg::ct_own && NO > 0) {  // H done: its reads of Zu are over (C^T lands there)
-    if (lane == 0) lds_signal(L.flag + 4);
-  }
   stamp.mark(1);
   // ---- wave 0: Quu^-1 by the symmetric sweep (overlaps waves 1-3) ----------
   if constexpr (W == 0) {
@@ -1032,17 +1043,17 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
       lds_wait_ge(L.flag + 1, target);
     }
     if (boxk) {
-      if (!box_gains_wave<MP, LDQ>(D, L, b, t, cur, lane) && lane == 0) *L.flag = 1;
+      if (!box_gains_wave<MP, LDQ, LDC>(D, L, b, t, cur, lane) && lane == 0) *L.flag = 1;
     } else {
-      // C = Lc^-1 into Qi (the gains as K = C^T (C Qxu^T), k = C^T (C Qu))
-      // (C^T over Zu: written once every wave's H tiles have read Zu)
-      const int htarget = Cfg::ct_own ? 0 : P.gwaves * (D.T - t);
+      // C = Lc^-1 into Qi (the gains as K = C^T (C Qxu^T), k = C^T (C Qu)), and C^T where
+      // it has an area of its own
+      double* const Ct = Cfg::ct_own ? L.Ct : nullptr;
       __builtin_amdgcn_s_setprio(3);  // the sweeps' latency chain is the knot's critical path
       bool bad;
       if constexpr (MP == 32)
-        bad = chol_inv_blocked2<LDQ, Cfg::LDT>(Quu, Qi, L.Ct, L.rowbuf, mu, lane, L.flag + 4, htarget);
+        bad = chol_inv_blocked2<LDQ, Cfg::LDT, LDC>(Quu, Qi, Ct, L.rowbuf, mu, lane);
       else
-        bad = chol_inv_sweep<MP, LDQ, Cfg::LDT>(Quu, Qi, L.Ct, L.rowbuf, mu, lane, L.flag + 4, htarget);
+        bad = chol_inv_sweep<MP, LDQ, Cfg::LDT, LDC>(Quu, Qi, Ct, L.rowbuf, mu, lane, nullptr, 0);
       __builtin_amdgcn_s_setprio(0);
       if (bad && lane == 0) *L.flag = 1;
     }
@@ -1056,22 +1067,17 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
     dma_barrier();
   stamp.mark(3);
   if (*L.flag) return false;
-  // the next knot's operands: right after B1, except in the 8-wave plan with C^T over Zu
-  // (after B2, once every C^T read is done)
-  constexpr bool early_dma = NW <= 4 || Cfg::ct_own;
-  // (with C^T over Zu: the Fx part now, the rest after B2)
-  constexpr bool split_dma = !early_dma && !pre && NDX > 0;
-  if constexpr (early_dma && !pre) issue_dma(3);
-  if constexpr (split_dma) issue_dma(1);
+  // the next knot's operands, right after B1: every reader of Z, Lx and Lu (G, H and the
+  // Qx / Qu sums) is behind this barrier, and nothing else lives in their buffers
+  if constexpr (!pre) issue_dma();
   // ---- P2: K(:, i) = Quu^-1 Qxu(i, :)^T ; Vxx(i, j) = Qxx(i, j) - K(:, i)^T Qxu(j, :)^T
   f64x4 Kt[NA][MTL];
   double kst = 0.;   // wave 0: k(row) (lanes part == 0)
   double vfs[NA];    // Vxx fs (lanes q == 0 of the x blocks)
-  // This knot's K, k and Vxx fs to HBM. With C^T in its own area (the small shapes) after
-  // B3: their stores would otherwise hold B3's vmcnt wait, and they drain while the next
-  // knot's G runs. The C5 shape stores them where they are formed (measured: deferring
-  // costs its spilling kernel 3 %).
-  constexpr bool defer = Cfg::ct_own;
+  // This knot's K, k and Vxx fs go to HBM after B3: their stores would otherwise hold B3's
+  // vmcnt wait, and they drain while the next knot's G runs. (The C5 shape stored them where
+  // they are formed while its LDS-DMA went after B2 and B3 waited for that anyway.)
+  constexpr bool running_sums = Cfg::ct_own;  // (else: per-knot wave sums, see P3)
   auto store_K = [&]() {
     double* Kg = D.K + rr * D.sNM;
 #pragma unroll
@@ -1114,28 +1120,31 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
         for (int s = 0; s < 4 * MTL; ++s) {
           const double bq = Qxu[(4 * s + q) * LDV + 16 * i + c];
 #pragma unroll
-          for (int it = 0; it < MTL; ++it) Kt[o][it] = mfma4(Qi[(4 * s + q) * LDQ + 16 * it + c], bq, Kt[o][it]);
+          for (int it = 0; it < MTL; ++it) Kt[o][it] = mfma4(Qi[(4 * s + q) * LDC + 16 * it + c], bq, Kt[o][it]);
         }
         if (!boxk) {
           // Kt holds W = C Qxu^T; K = C^T W: W's accumulator register s' holds rows
           // q + 4 s' of its 16-row tile, which is the B fragment of k-step s'. C is
           // lower triangular, so C^T's tile (it, kt) vanishes for kt < it: tile it of
           // K reads W's tiles kt >= it only, so it replaces W's tile it in place
-          // (one extra tile of registers, not MTL)
+          // (one extra tile of registers, not MTL). C^T(i, k) = C(k, i): from the copy at
+          // Ct[k * LDT + i], or out of C itself at Qi[i * LDC + k] (LDC odd: the 16 lanes
+          // of a fragment step along it)
 #pragma unroll
           for (int it = 0; it < MTL; ++it) {
             f64x4 kn = f64x4{0., 0., 0., 0.};
 #pragma unroll
             for (int kt = it; kt < MTL; ++kt)
 #pragma unroll
-              for (int s = 0; s < 4; ++s)
-                kn = mfma4(L.Ct[(16 * kt + 4 * s + q) * Cfg::LDT + 16 * it + c], Kt[o][kt][s], kn);
+              for (int s = 0; s < 4; ++s) {
+                const int ci = 16 * it + c, ck = 16 * kt + 4 * s + q;
+                kn = mfma4(Cfg::ct_own ? L.Ct[ck * Cfg::LDT + ci] : Qi[ci * LDC + ck], Kt[o][kt][s], kn);
+              }
             Kt[o][it] = kn;
           }
         }
       }
     }
-    if constexpr (!defer) store_K();
     stamp.mark(4);
     // this wave's V tiles (i, j), i <= j: with K(:, i) when it owns block i
     // ("row" form, V(i, j) = Qxx(i, j) - K(:, i)^T Qxu(j, :)^T), else with
@@ -1187,8 +1196,8 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
       if (!boxk) {
         // y = C Qu (into kv), then k = C^T y
         for (int k2 = part; k2 < mu; k2 += 2 * LPR) {
-          a0 = fma(Qi[k2 * LDQ + row], L.qu[k2], a0);
-          if (k2 + LPR < mu) a1 = fma(Qi[(k2 + LPR) * LDQ + row], L.qu[k2 + LPR], a1);
+          a0 = fma(Qi[k2 * LDC + row], L.qu[k2], a0);
+          if (k2 + LPR < mu) a1 = fma(Qi[(k2 + LPR) * LDC + row], L.qu[k2 + LPR], a1);
         }
         double a = a0 + a1;
 #pragma unroll
@@ -1197,9 +1206,10 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
         asm volatile("" ::: "memory");
         a0 = 0.;
         a1 = 0.;
+        auto ct = [&](int i, int k2) { return Cfg::ct_own ? L.Ct[k2 * Cfg::LDT + i] : Qi[i * LDC + k2]; };  // C(k2, i)
         for (int k2 = part; k2 < mu; k2 += 2 * LPR) {
-          a0 = fma(L.Ct[k2 * Cfg::LDT + row], L.kv[k2], a0);
-          if (k2 + LPR < mu) a1 = fma(L.Ct[(k2 + LPR) * Cfg::LDT + row], L.kv[k2 + LPR], a1);
+          a0 = fma(ct(row, k2), L.kv[k2], a0);
+          if (k2 + LPR < mu) a1 = fma(ct(row, k2 + LPR), L.kv[k2 + LPR], a1);
         }
         a = a0 + a1;
 #pragma unroll
@@ -1210,7 +1220,6 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
           L.kv[row] = a;
           kst = a;
         }
-        if constexpr (!defer) store_k();
       }
       asm volatile("" ::: "memory");
       double a;
@@ -1230,19 +1239,16 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
   stamp.mark(5);
   // B2 (partial, LDS counter): P3 (the x-block owners) needs every V tile
   // and wave 0's Quu k; the other waves only signal (when they produced
-  // something) and go on issuing the DMA.
+  // something) and go on to B3. (No buffer the LDS-DMA in flight writes is read or
+  // written by P2: C^T, where it has no area of its own, is read out of C, never laid
+  // over Zu.)
   if constexpr (W == 0 || P.owns_x(W)) {
     if (lane == 0) lds_signal(L.flag + 3);
   }
-  // With C^T over Zu (!ct_own) the next knot's LDS-DMA into Zu must also wait for every
-  // C^T read (the K products of the x-block owners, wave 0's k): the waves that only
-  // signal would otherwise issue it while those still run (a race seen as 1 in 256 solves
-  // differing between trial-group sizes)
-  if constexpr (P.owns_x(W) || (!Cfg::ct_own && NW == 8)) {
+  if constexpr (P.owns_x(W)) {
     const int target = (P.xwaves + (P.owns_x(0) ? 0 : 1)) * (D.T - t);
     lds_wait_ge(L.flag + 3, target);
   }
-  if constexpr (!early_dma) issue_dma(split_dma ? 2 : 3);
   // ---- P3: Vx = Qx + K^T Quuk - 2 K^T Qu (+ Vxx fs), reduction terms -------
   {
     const double* fsv = fsb;
@@ -1250,7 +1256,7 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
     double pv[5] = {0., 0., 0., 0., 0.};
 #pragma unroll
     for (int o = 0; o < NO; ++o) {
-      if constexpr (defer) vfs[o] = 0.;
+      vfs[o] = 0.;
       const int i = P.blk[W][o];
       if (i < NTL) {
         const int R = 16 * i + c;
@@ -1286,10 +1292,7 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
           if (R < n) {
             v = ur ? (L.qx[R] + a) - 2 * c2 : L.qx[R] - c2;
             if (!feas) {
-              if constexpr (defer)
-                vfs[o] = f;
-              else
-                D.Vxxfs[kk * D.sN + R] = f;
+              vfs[o] = f;
               v += f;
               pv[2] += v * fsv[R];
               pv[3] += fsv[R] * f;
@@ -1310,14 +1313,15 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
     // the expected-improvement / stopping terms. Small shapes: per-lane running sums over
     // the knots, reduced over the workgroup once at the end of the sweep; the C5 shape
     // (its kernel at the register cap): per-knot wave sums into D.part
-    if constexpr (defer) {
+    if constexpr (running_sums) {
 #pragma unroll
       for (int j = 0; j < 5; ++j) red5[j] += pv[j];
     } else {
 #pragma unroll
       for (int j = 0; j < 5; ++j) {
+        if (P.rslot[j][W] < 0) continue;  // no term of this sum on this wave
         const double s = wave_sum(pv[j]);
-        if (lane == 0) L.red[j * NW + W] = s;
+        if (lane == 0) L.red[P.rslot[j][W]] = s;
       }
     }
     if (bad) *L.flag = 1;
@@ -1328,11 +1332,9 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
   if constexpr (P.dmarank[W] >= 0 && !pre) {
     if (t > 0) dma_vec<P.ndma>(L.fsb, D.fs + (kk - 1) * D.sN, n, P.dmarank[W], lane);
   }
-  if constexpr (defer) {
-    store_K();
-    store_fs();
-    store_k();
-  }
+  store_K();
+  store_fs();
+  store_k();
   return true;
 }
 
@@ -1363,7 +1365,7 @@ __device__ __forceinline__ bool bwd_sweep_mfma(const Dev& D, int b, bool feas, d
   L.flag = (int*)(sm + Cfg::oFlag);
   L.Zx = sm + Cfg::oZx;
   L.Zu = sm + Cfg::oZu;
-  L.Ct = sm + Cfg::oCt;
+  L.Ct = sm + Cfg::oCt;  // (ct_own only; else C^T is read out of Qi)
   constexpr bool pre = BwdPlan<NTL, MTL, NW>{}.prefetch;
   L.Zx2 = pre ? sm + Cfg::oZx2 : L.Zx;
   L.Zu2 = pre ? sm + Cfg::oZu2 : L.Zu;
@@ -1372,7 +1374,6 @@ __device__ __forceinline__ bool bwd_sweep_mfma(const Dev& D, int b, bool feas, d
   L.fsb2 = pre ? sm + Cfg::oFs2 : L.fsb;
   L.cb0 = sm + Cfg::oCb;
   L.cb1 = sm + Cfg::oCb + Cfg::CB;
-  static_assert(Cfg::ct_own || NW == 8, "C^T over Zu needs the 8-wave plan's late LDS-DMA");
   double* V = L.V;
   const bool xr = !isnan(xreg);
   Stamp stamp(D.stamps ? D.stamps + ((int64_t)b * 8 + wid) * 8 : nullptr);
@@ -1382,7 +1383,7 @@ __device__ __forceinline__ bool bwd_sweep_mfma(const Dev& D, int b, bool feas, d
     L.flag[1] = 0;  // Quu-ready counter (8-wave plan)
     L.flag[2] = 0;  // G-done counter (partial B0)
     L.flag[3] = 0;  // P2-done counter (partial B2)
-    L.flag[4] = 0;  // H-done counter (C^T over Zu)
+    L.flag[4] = 0;  // (spare)
   }
   // ---- terminal: Vxx = Lxx_T (+ xreg I), Vx = Lx_T (+ Vxx fs_T) ------------
   {
@@ -1481,10 +1482,13 @@ __device__ __forceinline__ bool bwd_sweep_mfma(const Dev& D, int b, bool feas, d
       if (tid == 0) {
         double* p = D.part + kk * 8;
         const double* red = L.red;
+        constexpr BwdPlan<NTL, MTL, NW> P{};
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
           double a = 0.;
-          for (int w = 0; w < NW; ++w) a += red[j * NW + w];
+#pragma unroll
+          for (int w = 0; w < NW; ++w)
+            if (P.rslot[j][w] >= 0) a += red[P.rslot[j][w]];
           p[j] = a;
         }
       }

@@ -22,7 +22,7 @@ __global__ void k_sweep(const double* Q, double* Qi_out, unsigned long long* cyc
     else if (variant == 1)
       bad |= fddp::chol_inv_sweep<32, 32, 33>(Quu, Qi, Ct, rb, m, lane, nullptr, 0);
     else if (variant == 2)
-      bad |= fddp::chol_inv_blocked2<32, 33>(Quu, Qi, Ct, rb, m, lane, nullptr, 0);
+      bad |= fddp::chol_inv_blocked2<32, 33>(Quu, Qi, Ct, rb, m, lane);
     else
       bad |= fddp::chol_inv_sweep<16, 32, 33>(Quu, Qi, Ct, rb, m < 16 ? m : 16, lane, nullptr, 0);
   }
