@@ -151,7 +151,11 @@ typedef struct {
   int32_t kind;          /* FDDP_KNOT_* */
   int32_t nu;            /* controls of this knot's model (0 allowed for running knots) */
   int64_t param_offset;  /* offset (doubles) of this knot's block in the parameter pool */
-  int64_t param_stride;  /* doubles between batch elements' blocks; 0 = block shared by all */
+  int64_t param_stride;  /* doubles between batch elements' blocks; 0 = block shared by all.
+                          * The blocks of different elements may differ in every value but, per
+                          * knot, not in structure (kind, nu, the counts and sizes in the block);
+                          * a stride may be odd (blocks need no 16-byte alignment), and knots of
+                          * one horizon may mix strides. */
 } fddp_knot_desc;
 
 /* Solver thresholds; defaults = reference constructors
