@@ -53,12 +53,8 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // longer on the sweep's critical path; dependent f64 FMA latency is 32 cycles)
 __device__ __forceinline__ double rcp_f64(double d) {
   double x = __builtin_amdgcn_rcp(d);
-#ifndef FDDP_RCP_NO_NEWTON
   x = fma(fma(-d, x, 1.), x, x);
-#ifndef FDDP_RCP_ONE_NEWTON
   x = fma(fma(-d, x, 1.), x, x);
-#endif
-#endif
   return x;
 }
 
@@ -414,80 +410,6 @@ __device__ __forceinline__ bool chol_inv_blocked2(const double* Quu, double* C, 
       Ct[i * LDT + j] = C[j * LDC + i];
     }
   }
-  return bad;
-}
-
-// Same sweep with each lane owning a BS x BS block of the matrix (BS = MP/8,
-// an 8 x 8 grid of blocks over the 64 lanes): per step one FMA per element
-// as before, but the column-k / row-k fix-ups touch BS elements of 8 lanes
-// instead of MP elements of 2 lanes, and the broadcast reads are 2 x BS
-// contiguous doubles. VALU-issue bound (f64 ops issue at 8 cycles), so this
-// is ~1.8x fewer cycles per pivot than the column-per-lane layout.
-template <int MP, int LDQ>
-__device__ __forceinline__ bool sym_sweep_inverse_blk(const double* Quu, double* Qi, double* rb, int m, int lane) {
-  constexpr int BS = MP / 8;
-  static_assert(MP % 8 == 0 && BS >= 1, "8 x 8 lane grid");
-  const int bi = lane >> 3, bj = lane & 7;
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  double A[BS][BS];
-#pragma unroll
-  for (int a = 0; a < BS; ++a)
-#pragma unroll
-    for (int b = 0; b < BS; ++b) A[a][b] = Quu[(BS * bj + b) * LDQ + BS * bi + a];
-  bool bad = false;
-  if (bi == 0) {
-#pragma unroll
-    for (int b = 0; b < BS; ++b) rb[BS * bj + b] = A[0][b];
-  }
-#pragma unroll
-  for (int k = 0; k < MP; ++k) {
-    if (k < m) {
-      const int kb = k / BS, kr = k % BS;
-      const int k1 = k + 1, kb1 = k1 / BS, kr1 = k1 % BS;
-      (void)k1;
-      asm volatile("" ::: "memory");
-      const double d = rb[k];
-      double rowv[BS], colv[BS];
-#pragma unroll
-      for (int b = 0; b < BS; ++b) rowv[b] = rb[BS * bj + b];  // A(k, my columns)
-#pragma unroll
-      for (int a = 0; a < BS; ++a) colv[a] = rb[BS * bi + a];  // A(my rows, k) by symmetry
-      bad |= !(d > 0.);
-      const double dinv = rcp_f64(d);
-      double w[BS];
-#pragma unroll
-      for (int b = 0; b < BS; ++b) w[b] = rowv[b] * dinv;
-      const bool colk = bj == kb, rowk = bi == kb;
-      auto fix = [&](int a, int b, double v) {  // column-k / row-k / (k, k) fix-ups
-        if (colk && b == kr) v = colv[a] * dinv;
-        if (rowk && a == kr) v = (colk && b == kr) ? -dinv : w[b];
-        return v;
-      };
-      // next step's row first (register row kr1 holds it in lanes bi == kb1;
-      // after the last pivot the publish is dead and harmless)
-#pragma unroll
-      for (int b = 0; b < BS; ++b) A[kr1][b] = fix(kr1, b, fma(-colv[kr1], w[b], A[kr1][b]));
-      asm volatile("" ::: "memory");
-      if (bi == kb1) {
-#pragma unroll
-        for (int b = 0; b < BS; ++b) rb[BS * bj + b] = A[kr1][b];
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int a = 0; a < BS; ++a) {
-        if (a == kr1) continue;
-#pragma unroll
-        for (int b = 0; b < BS; ++b) A[a][b] = fix(a, b, fma(-colv[a], w[b], A[a][b]));
-      }
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < BS; ++a)
-#pragma unroll
-    for (int b = 0; b < BS; ++b) {
-      const int i = BS * bi + a, j = BS * bj + b;
-      Qi[j * LDQ + i] = (i < m && j < m) ? -A[a][b] : 0.;
-    }
   return bad;
 }
 

@@ -3,10 +3,10 @@
 // multibody-only variants at three / two waves per EU (the large ones), so they compile in
 // parallel.
 // The rollout's knot calc solves [M | Jc^T | tau - nle] by the dense blocked Gauss-Jordan
-// (multibody.hpp MB_CALC_DENSE): measured on the C5 walk, the tree-sparse LTDL with the
-// cost records on its idle waves has to be called out of line here (the backend's register
-// alignment check trips on it inlined at the 256-VGPR cap), and the calls cost the rollout
-// 6 % (29.9 -> 31.8 ms per step), more than the solve gains.
+// (multibody.hpp MB_CALC_DENSE): the tree-sparse LTDL with the cost records on its idle waves
+// does not build inlined here (the backend's register alignment check trips on it at the
+// 256-VGPR cap), and measured on the C5 walk out of line its calls cost the rollout 6 %
+// (29.9 -> 31.8 ms per step), more than the solve gains.
 #define MB_CALC_DENSE 1
 // the multibody-only variants keep the knot's parsed block header in scalar registers
 // (multibody.hpp MB_BLK_UNIFORM) and give every phase of the calc a fresh copy of its lane

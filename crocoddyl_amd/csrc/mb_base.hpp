@@ -1,0 +1,241 @@
+// Multibody knots, the common ground: the hooks the diagnostic tools define, the stores and
+// LDS accessors all the multibody code uses, the constants and record types, and the
+// parameter-block header (Blk, parse, parse_uniform).
+#pragma once
+
+#include <type_traits>
+
+#include "fddp_device.hpp"
+
+// Everything except the workgroup drivers (knot_calc, knot_calc_diff,
+// gauss_jordan) is __host__ __device__, so the same arithmetic is unit-tested
+// on the CPU against the oracle (tests/test_multibody_host.py).
+#define MB_HD __host__ __device__
+
+// Diagnostic hooks, empty in the library. A tool or the host harness defines one before it
+// includes multibody.hpp (tools/mb_probe.hip: all three; tools/gj_bench.hip: MB_GJ_MARK;
+// tests/cpp/mb_host.cpp: MB_DUMP):
+//   MB_DUMP copies an LDS matrix, rows x cols at leading dimension ld, out of the calcDiff
+//     for the parity diagnosis; every thread calls it between phases.
+//   MB_GJ_MARK(id) stamps a phase boundary of gj_mfma, tree_ltdl_wave and the calcDiff.
+//   MB_TILE_* count the cycles of thread 0 inside the tile loops of the calcDiff's
+//     matrix-core products, summed over its tiles in registers: MB_TILE_LAP(k) adds the time
+//     since the last lap to sum k, after the operands named in MB_TILE_PIN4 have arrived;
+//     MB_TILE_FLUSH(base) stores the sums and the tile count.
+#ifndef MB_DUMP
+#define MB_DUMP(slot, ptr, rows, cols, ld)
+#endif
+#ifndef MB_GJ_MARK
+#define MB_GJ_MARK(id)
+#endif
+#ifndef MB_TILE_DECL
+#define MB_TILE_DECL
+#define MB_TILE_START(n)
+#define MB_TILE_PIN4(a)
+#define MB_TILE_LAP(k)
+#define MB_TILE_FLUSH(base)
+#endif
+
+// On the device every multibody record (parameter block) and the work area live in
+// LDS; the record / work-area accessors re-assert it where the pointer is formed, so
+// the accesses compile to ds_* even where the address-space inference loses the
+// entry's assumption (flat accesses to LDS pay a full round trip each). The host
+// emulation (tests/cpp/mb_host.cpp) reads ordinary memory.
+// A store to the caller's output blocks, which are in HBM: through a global pointer,
+// so the compiler emits global_store instead of a flat store that every later LDS
+// access of the wave must wait behind (flat may alias LDS).
+MB_HD __forceinline__ void mb_gstore(double* p, double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  *(__attribute__((address_space(1))) double*)p = v;
+#else
+  *p = v;
+#endif
+}
+// two consecutive doubles (16-B aligned) in one store
+MB_HD __forceinline__ void mb_gstore2(double* p, double v0, double v1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  *(__attribute__((address_space(1))) double2*)p = make_double2(v0, v1);
+#else
+  p[0] = v0;
+  p[1] = v1;
+#endif
+}
+// A fresh register copy of v (device: an empty asm the optimiser cannot see through), so
+// a value live across the whole kernel is reloaded from its spill slot once, here.
+template <class T>
+MB_HD __forceinline__ T mb_launder(T v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (sizeof(T) == 8) {
+    long long x;
+    __builtin_memcpy(&x, &v, 8);
+    asm volatile("" : "+v"(x));
+    __builtin_memcpy(&v, &x, 8);
+  } else {
+    int x;
+    __builtin_memcpy(&x, &v, 4);
+    asm volatile("" : "+v"(x));
+    __builtin_memcpy(&v, &x, 4);
+  }
+#endif
+  return v;
+}
+template <class T>
+MB_HD __forceinline__ T* mb_lds(T* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return ::fddp::lds_ptr(p);
+#else
+  return p;
+#endif
+}
+
+// MB_LANE_OPAQUE (per kernel object): every phase of the device executor gets its lane index
+// as a fresh register copy, so what a phase derives from it (addresses, lane masks) is formed
+// in the phase and not hoisted out of the caller's knot loop, to be held across every other
+// phase at the register cap.
+#ifndef MB_LANE_OPAQUE
+#define MB_LANE_OPAQUE 0
+#endif
+
+namespace fddp {
+namespace mb {
+
+typedef unsigned long long Mask;  // one bit per dof
+constexpr int kMaxJ = 64;         // dofs (nv)
+constexpr int kJRec = 27;         // doubles per joint record
+constexpr int kCHdr = 4;          // doubles of a cost record's header
+constexpr int kMaxJacCosts = 8;   // costs with a dense residual Jacobian (frame, CoM, free-flyer state)
+constexpr int kMaxNc = 24;        // stacked contact rows (FDDP_KNOT_EULER_CONTACTFWD)
+constexpr int kMbDiffNT = 256;    // threads of the knot-parallel calcDiff workgroup
+enum { J_REVOLUTE = 0, J_FREEFLYER = 1 };
+// Cost record types; contact records (after the costs) use 5 / 6 and the same
+// frame payload as the frame costs, so frame_residual serves both.
+enum {
+  C_STATE = 1,
+  C_CONTROL = 2,
+  C_FRAME_PLACEMENT = 3,
+  C_FRAME_TRANSLATION = 4,
+  C_CONTACT_3D = 5,
+  C_CONTACT_6D = 6,
+  C_CONTACT_FORCE = 7,  // cost on a contact's force: payload [row0, nr, fref(6)] (contact-force.hxx)
+  C_COM_POSITION = 8,   // r = com(q) - cref: payload [cref(3)] (com-position.hxx:49-75)
+  C_FRICTION_CONE = 9,  // r = A lambda_lin: payload [row0, nc, nr, A (nr x 3 row-major)]
+                        // (contact-friction-cone.hxx:51-91)
+  C_FRAME_VELOCITY = 10  // r = LOCAL frame velocity - vref: frame payload + vref(6) (frame-velocity.hxx:53-84)
+};
+// Activation of a cost record: header slot 2 (core/activations/*.hpp)
+enum { A_QUAD = 0, A_WEIGHTED_QUAD = 1, A_QUAD_BARRIER = 2, A_WEIGHTED_QUAD_BARRIER = 3 };
+constexpr int kInactiveForceRow = -2;  // contact-force cost on an inactive contact: lambda = 0, no Jacobians
+
+struct Blk {
+  double dt;
+  int nj;   // nv: dofs
+  int nq;   // nv + 1 with a free-flyer root
+  int nb;   // joint records (pinocchio joints)
+  bool ff;  // record 0 is a free-flyer (dofs 0..5: base twist, body on dof 5)
+  int ncost;
+  const double* g;    // gravity (3)
+  const double* arm;  // armature (nv)
+  const double* J;    // joint records
+  const double* C;    // cost records
+  // contact section (DifferentialActionModelContactFwdDynamics); ncon == 0 without
+  int nun;            // leading unactuated dofs: tau = [0_nun; u], nu = nj - nun
+  int ncon, nc;       // active contact records, stacked rows
+  double damping;     // JMinvJt_damping
+  const double* K;    // contact records
+  // impulse section instead (ActionModelImpulseFwdDynamics, nu = 0)
+  bool impulse;
+  double r_coeff;     // restitution coefficient
+  bool enable_force;  // contact section flag 2: force Jacobians for CostModelContactForce
+};
+
+MB_HD inline Blk parse(const double* P) {
+  Blk b;
+  b.dt = P[0];
+  b.nj = (int)P[1];
+  b.ncost = (int)P[2];
+  b.g = P + FDDP_PARAM_HEADER;
+  b.arm = b.g + 3;
+  b.J = b.arm + b.nj;
+  b.ff = (int)b.J[0] == J_FREEFLYER;
+  b.nb = b.ff ? b.nj - 5 : b.nj;
+  b.nq = b.ff ? b.nj + 1 : b.nj;
+  b.C = b.J + (int64_t)kJRec * b.nb;
+  const double* e = b.C;
+  for (int k = 0; k < b.ncost; ++k) e += (int)e[3];
+  b.nun = 0;
+  b.ncon = b.nc = 0;
+  b.damping = 0.;
+  b.K = e;
+  b.impulse = false;
+  b.enable_force = false;
+  b.r_coeff = 0.;
+  if (e - P < (int64_t)P[3]) {  // [nun | r_coeff, damping, ncontact, 0 | 1 | 2] + records
+    b.impulse = (int)e[3] == 1;
+    b.enable_force = (int)e[3] == 2;
+    b.nun = b.impulse ? b.nj : (int)e[0];
+    b.r_coeff = b.impulse ? e[0] : 0.;
+    b.damping = e[1];
+    b.ncon = (int)e[2];
+    b.K = e + 4;
+    const double* r = b.K;
+    for (int k = 0; k < b.ncon; ++k) {
+      b.nc += (int)r[0] == C_CONTACT_3D ? 3 : 6;
+      r += (int)r[3];
+    }
+  }
+  return b;
+}
+
+// MB_BLK_UNIFORM (per kernel object, as MB_MFMA_SCALAR_SHAPE): the header parsed from the
+// LDS-staged block is the same in every lane, but arrives in vector registers and stays live
+// through the whole calc. parse_uniform moves every field into scalar registers (the first
+// lane's value; doubles in two halves, the LDS pointers by their 32-bit LDS address, so they
+// keep their address space). The host path is parse itself.
+#ifndef MB_BLK_UNIFORM
+#define MB_BLK_UNIFORM 0
+#endif
+#if MB_BLK_UNIFORM && defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ int mb_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ bool mb_uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
+__device__ __forceinline__ double mb_uniform(double v) {
+  int h[2];
+  __builtin_memcpy(h, &v, 8);
+  h[0] = __builtin_amdgcn_readfirstlane(h[0]);
+  h[1] = __builtin_amdgcn_readfirstlane(h[1]);
+  __builtin_memcpy(&v, h, 8);
+  return v;
+}
+__device__ __forceinline__ const double* mb_uniform(const double* p) {
+  typedef const __attribute__((address_space(3))) double* LdsP;
+  const unsigned a = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(LdsP)p);
+  return (const double*)(LdsP)(size_t)a;
+}
+#endif
+// P: the block in LDS (device)
+MB_HD __forceinline__ Blk parse_uniform(const double* P) {
+  Blk b = parse(P);
+#if MB_BLK_UNIFORM && defined(__HIP_DEVICE_COMPILE__)
+  b.dt = mb_uniform(b.dt);
+  b.nj = mb_uniform(b.nj);
+  b.nq = mb_uniform(b.nq);
+  b.nb = mb_uniform(b.nb);
+  b.ff = mb_uniform(b.ff);
+  b.ncost = mb_uniform(b.ncost);
+  b.g = mb_uniform(b.g);
+  b.arm = mb_uniform(b.arm);
+  b.J = mb_uniform(b.J);
+  b.C = mb_uniform(b.C);
+  b.nun = mb_uniform(b.nun);
+  b.ncon = mb_uniform(b.ncon);
+  b.nc = mb_uniform(b.nc);
+  b.damping = mb_uniform(b.damping);
+  b.K = mb_uniform(b.K);
+  b.impulse = mb_uniform(b.impulse);
+  b.r_coeff = mb_uniform(b.r_coeff);
+  b.enable_force = mb_uniform(b.enable_force);
+#endif
+  return b;
+}
+
+}  // namespace mb
+}  // namespace fddp

@@ -1,0 +1,447 @@
+// Multibody knots, cost and contact records: CRec, the activations (Act), residuals and
+// their Jacobians, the cost counts that size the calcDiff's plan, the contact rows.
+#pragma once
+
+#include "mb_se3.hpp"
+#include "mb_world.hpp"
+
+namespace fddp {
+namespace mb {
+
+// Cost records
+struct CRec {
+  const double* r;
+  MB_HD int type() const { return (int)mb_lds(r)[0]; }
+  MB_HD double weight() const { return mb_lds(r)[1]; }
+  MB_HD int size() const { return (int)mb_lds(r)[3]; }
+  MB_HD const double* d() const { return mb_lds(r + kCHdr); }
+};
+
+// dof carrying the frame of a frame / contact payload d = [joint record, R 9, p 3, ...]
+MB_HD __forceinline__ int frame_dof(const Blk& b, const double* d) { return dof_of_rec(b, (int)d[0]); }
+
+// oMf of a frame payload
+MB_HD inline void frame_placement(const Blk& b, const WVals& V, const double* d, double* R, double* p) {
+  const int j = frame_dof(b, d);
+  matmul3(V.oR(j), d + 1, R);
+  matvec3(V.oR(j), d + 10, p);
+  p[0] += V.op(j)[0];
+  p[1] += V.op(j)[1];
+  p[2] += V.op(j)[2];
+}
+
+// Residual of a frame cost and, with S != null (the world motion of a dof that
+// moves the frame), its Jacobian column. Returns the residual size (6 placement,
+// 3 translation).
+MB_HD inline int frame_residual(const Blk& b, const WVals& V, const CRec& C, const double* S, double* r, double* Jc) {
+  const double* d = C.d();
+  double Rf[9], pf[3];
+  frame_placement(b, V, d, Rf, pf);
+  double dR[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.}, dp[3] = {0., 0., 0.};
+  if (S) {  // motion of oMf under S: dp = S_lin + S_ang x pf, dR = [S_ang]x Rf
+    double t[3];
+    cross3(S + 3, pf, t);
+    for (int e = 0; e < 3; ++e) dp[e] = S[e] + t[e];
+    for (int c = 0; c < 3; ++c) cross3(S + 3, Rf + 3 * c, dR + 3 * c);
+  }
+  if (C.type() == C_FRAME_TRANSLATION || C.type() == C_CONTACT_3D) {
+    const double* pref = d + 13;
+    for (int e = 0; e < 3; ++e) {
+      r[e] = pf[e] - pref[e];
+      if (Jc) Jc[e] = dp[e];
+    }
+    for (int e = 3; e < 6; ++e) {
+      r[e] = 0.;
+      if (Jc) Jc[e] = 0.;
+    }
+    return 3;
+  }
+  // rMf = Mref^-1 oMf
+  const double* Rri = d + 13;
+  const double* pri = d + 22;
+  double Rr[9], pr[3], dRr[9], dpr[3];
+  matmul3(Rri, Rf, Rr);
+  matvec3(Rri, pf, pr);
+  pr[0] += pri[0];
+  pr[1] += pri[1];
+  pr[2] += pri[2];
+  matmul3(Rri, dR, dRr);
+  matvec3(Rri, dp, dpr);
+  Dual RD[9], PD[3], o[6];
+  for (int e = 0; e < 9; ++e) RD[e] = Dual{Rr[e], dRr[e]};
+  for (int e = 0; e < 3; ++e) PD[e] = Dual{pr[e], dpr[e]};
+  log6_t<Dual>(RD, PD, o);
+  for (int e = 0; e < 6; ++e) {
+    r[e] = o[e].v;
+    if (Jc) Jc[e] = S ? o[e].d : 0.;
+  }
+  return 6;
+}
+
+// Residual size of a cost record.
+MB_HD inline int cost_nr(const Blk& b, const CRec& C, int nu) {
+  const int t = C.type();
+  if (t == C_CONTACT_FORCE) return (int)C.d()[1];
+  if (t == C_FRICTION_CONE) return (int)C.d()[2];
+  if (t == C_STATE) return 2 * b.nj;
+  if (t == C_CONTROL) return nu;
+  return (t == C_FRAME_PLACEMENT || t == C_FRAME_VELOCITY) ? 6 : 3;
+}
+// The activation of a cost record (its parameters end the record):
+//   Quad / WeightedQuad (quadratic.hpp, weighted-quadratic.hpp:42-71): w (ones if
+//     unweighted); a = 0.5 w r^2, Ar = w r, Arr = w
+//   QuadraticBarrier (quadratic-barrier.hpp:88-117): lb, ub; with rl = min(r - lb, 0),
+//     ru = max(r - ub, 0): a = 0.5 (rl^2 + ru^2), Ar = rl + ru, Arr = [r <= lb or r >= ub]
+//   WeightedQuadraticBarrier (weighted-quadratic-barrier.hpp:35-70): lb, ub, w;
+//     a = 0.5 w^2 (rl^2 + ru^2), Ar = w^2 (rl + ru), Arr = w [r <= lb or r >= ub]
+// Per residual row i: value2 (twice its share of a: callers sum the rows, then
+// halve), sgrad (X * Ar_i, as (X w) r for the quadratic kinds), hess (Arr_ii).
+struct Act {
+  int kind, nr;
+  const double* p;
+  MB_HD __forceinline__ double value2(int i, double r) const {
+    const double* p = mb_lds(this->p);
+    if (kind <= A_WEIGHTED_QUAD) return p[i] * r * r;
+    const double rl = fmin(r - p[i], 0.), ru = fmax(r - p[nr + i], 0.);
+    const double v = rl * rl + ru * ru;
+    return kind == A_WEIGHTED_QUAD_BARRIER ? p[2 * nr + i] * p[2 * nr + i] * v : v;
+  }
+  MB_HD __forceinline__ double sgrad(int i, double r, double X) const {
+    const double* p = mb_lds(this->p);
+    if (kind <= A_WEIGHTED_QUAD) return X * p[i] * r;
+    const double g = fmin(r - p[i], 0.) + fmax(r - p[nr + i], 0.);
+    return X * (kind == A_WEIGHTED_QUAD_BARRIER ? p[2 * nr + i] * p[2 * nr + i] * g : g);
+  }
+  MB_HD __forceinline__ double hess(int i, double r) const {
+    const double* p = mb_lds(this->p);
+    if (kind <= A_WEIGHTED_QUAD) return p[i];
+    const double h = (r - p[i] <= 0.) ? 1. : ((r - p[nr + i] >= 0.) ? 1. : 0.);
+    return kind == A_WEIGHTED_QUAD_BARRIER ? p[2 * nr + i] * h : h;
+  }
+};
+MB_HD inline Act cost_act(const Blk& b, const CRec& C, int nu) {
+  const int nr = cost_nr(b, C, nu), kind = (int)C.r[2];
+  const int np = kind <= A_WEIGHTED_QUAD ? nr : (kind == A_QUAD_BARRIER ? 2 * nr : 3 * nr);
+  return Act{kind, nr, C.r + C.size() - np};
+}
+// costs whose residual Jacobian is dense over the configuration tangent (stored
+// per cost: rows x jw, jw = nj, or 2 nj when a frame-velocity cost needs the
+// velocity columns too): frame costs, CoM, frame velocity, and the free-flyer
+// block of a state cost
+MB_HD __forceinline__ bool jac_cost(const Blk& b, int type) {
+  return type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_COM_POSITION ||
+         type == C_FRAME_VELOCITY || (type == C_STATE && b.ff);
+}
+MB_HD __forceinline__ int jac_rows(int type) {
+  return (type == C_FRAME_TRANSLATION || type == C_COM_POSITION) ? 3 : 6;
+}
+MB_HD inline int count_jac_costs(const Blk& b, bool* vel_cols = nullptr) {
+  int n = 0;
+  bool fv = false;
+  const double* cr = b.C;
+  for (int k = 0; k < b.ncost; ++k) {
+    const CRec C{cr};
+    if (jac_cost(b, C.type())) ++n;
+    if (C.type() == C_FRAME_VELOCITY) fv = true;
+    cr += C.size();
+  }
+  if (vel_cols) *vel_cols = fv;
+  return n;
+}
+// costs on the contact multipliers: CostModelContactForce, CostModelContactFrictionCone
+MB_HD __forceinline__ bool force_cost(int type) { return type == C_CONTACT_FORCE || type == C_FRICTION_CONE; }
+// Residual rows with a dense Jacobian (jac costs; force costs on an active contact
+// when the force Jacobians are computed): the rows of the stacked R of calcDiff.
+MB_HD inline int count_cost_rows(const Blk& b, int nu) {
+  int n = 0;
+  const bool fd = b.enable_force && b.nc > 0 && !b.impulse;
+  const double* cr = b.C;
+  for (int k = 0; k < b.ncost; ++k) {
+    const CRec C{cr};
+    if (jac_cost(b, C.type())) n += jac_rows(C.type());
+    if (fd && force_cost(C.type()) && (int)C.d()[0] >= 0) n += cost_nr(b, C, nu);
+    cr += C.size();
+  }
+  return n;
+}
+// row i of a force cost's residual from the multipliers lam of the contact rows
+// [row0, row0 + nc) (lam unread for an inactive contact: lambda = 0):
+//   contact force: lambda_i - fref_i (contact-force.hxx:33-50: jMf.actInv(f) is the multiplier);
+//   friction cone: A_i . lambda_lin (contact-friction-cone.hxx:58)
+// (lam(k): multiplier k, so that the calc reads it where it lies, sign applied at the use)
+template <class L>
+MB_HD __forceinline__ double force_res_at(const CRec& C, L lam, int i) {
+  const double* d = C.d();
+  const int row0 = (int)d[0];
+  if (C.type() == C_CONTACT_FORCE) return (row0 >= 0 ? lam(row0 + i) : 0.) - d[2 + i];
+  if (row0 < 0) return 0.;
+  const double* A = d + 3 + 3 * i;
+  return A[0] * lam(row0) + A[1] * lam(row0 + 1) + A[2] * lam(row0 + 2);
+}
+MB_HD __forceinline__ double force_res(const CRec& C, const double* lam, int i) {
+  return force_res_at(C, [lam](int k) { return lam[k]; }, i);
+}
+// row i of a force cost's Jacobian column from the multiplier Jacobian column
+// dl[row * ld] (the same linear map as force_res, without the offset)
+MB_HD __forceinline__ double force_jac(const CRec& C, const double* dl, int64_t ld, int i) {
+  const double* d = C.d();
+  const int row0 = (int)d[0];
+  if (C.type() == C_CONTACT_FORCE) return dl[(int64_t)(row0 + i) * ld];
+  const double* A = d + 3 + 3 * i;
+  return A[0] * dl[(int64_t)row0 * ld] + A[1] * dl[(int64_t)(row0 + 1) * ld] + A[2] * dl[(int64_t)(row0 + 2) * ld];
+}
+// activation value of a force cost (inactive contact: lambda = 0)
+template <class L>
+MB_HD __forceinline__ double force_cost_activation_at(const Blk& b, const CRec& C, L lam, int nu) {
+  const Act act = cost_act(b, C, nu);
+  double a = 0.;
+  for (int e = 0; e < act.nr; ++e) a += act.value2(e, force_res_at(C, lam, e));
+  return 0.5 * a;
+}
+MB_HD inline double force_cost_activation(const Blk& b, const CRec& C, const double* lam, int nu) {
+  return force_cost_activation_at(b, C, [lam](int k) { return lam[k]; }, nu);
+}
+
+// Residual of a frame cost, value only (calc). Returns the residual size.
+MB_HD __forceinline__ int frame_residual_value(const Blk& b, const WVals& V, const CRec& C, double* r) {
+  const double* d = C.d();
+  double Rf[9], pf[3];
+  frame_placement(b, V, d, Rf, pf);
+  if (C.type() == C_FRAME_TRANSLATION || C.type() == C_CONTACT_3D) {
+    for (int e = 0; e < 3; ++e) r[e] = pf[e] - d[13 + e];
+    return 3;
+  }
+  double Rr[9], pr[3];
+  matmul3(d + 13, Rf, Rr);
+  matvec3(d + 13, pf, pr);
+  for (int e = 0; e < 3; ++e) pr[e] += d[22 + e];
+  log6_t<double>(Rr, pr, r);
+  return 6;
+}
+
+// Centre of mass (pinocchio::centerOfMass) from the world body CoMs
+MB_HD inline void com_value(const Blk& b, const WVals& W, double* c) {
+  double m = 0., h[3] = {0., 0., 0.};
+  for (int k = 0; k < b.nj; ++k) {
+    if (!carries_body(b, k)) continue;
+    const double mk = *W.m(k);
+    m += mk;
+    for (int e = 0; e < 3; ++e) h[e] += mk * W.c(k)[e];
+  }
+  for (int e = 0; e < 3; ++e) c[e] = h[e] / m;
+}
+
+// free-flyer block of a state residual: log6(Mref^-1 M) (multibody.hxx:69)
+MB_HD inline void ff_rel(const double* xref, const double* x, double* Rr, double* pr) {
+  double R0[9], R1[9], dp[3];
+  quat_to_R(xref + 3, R0);
+  quat_to_R(x + 3, R1);
+  matTmul3(R0, R1, Rr);
+  for (int e = 0; e < 3; ++e) dp[e] = x[e] - xref[e];
+  matTvec3(R0, dp, pr);
+}
+
+// entry i of the state residual diff(xref, x) beyond the free-flyer block
+MB_HD __forceinline__ double state_res(const Blk& b, const double* xref, const double* x, int i) {
+  if (i < b.nj) return x[qof(b, i)] - xref[qof(b, i)];
+  return x[b.nq + i - b.nj] - xref[b.nq + i - b.nj];
+}
+
+// LOCAL velocity of a frame payload d minus vref (pinocchio::getFrameVelocity,
+// frame-velocity.hxx:57-59), from the world body velocities in V.
+MB_HD inline void frame_velocity_res(const Blk& b, const WVals& V, const double* d, double* r) {
+  const int j = frame_dof(b, d);
+  double Rf[9], pf[3], m6[6];
+  frame_placement(b, V, d, Rf, pf);
+  for (int e = 0; e < 6; ++e) m6[e] = V.v(j)[e];
+  motion_act_inv(Rf, pf, m6, r);
+  for (int e = 0; e < 6; ++e) r[e] -= d[13 + e];
+}
+
+// Activation value of one cost record (kinematics in V; velocities in V only with
+// vel: frame-velocity costs are skipped without). Force costs return 0: they need
+// the multipliers and are added after the contact solve.
+MB_HD __forceinline__ double cost_activation(const Blk& b, const WVals& V, const CRec& C, const double* x,
+                                             const double* u, int nu, bool vel = true) {
+  const Act act = cost_act(b, C, nu);
+  double a = 0.;
+  if (C.type() == C_STATE) {
+    const int ndx = 2 * b.nj;
+    int i0 = 0;
+    if (b.ff) {
+      double Rr[9], pr[3], r[6];
+      ff_rel(C.d(), x, Rr, pr);
+      log6_t<double>(Rr, pr, r);
+      for (int e = 0; e < 6; ++e) a += act.value2(e, r[e]);
+      i0 = 6;
+    }
+    for (int i = i0; i < ndx; ++i) a += act.value2(i, state_res(b, C.d(), x, i));
+  } else if (C.type() == C_CONTROL) {
+    for (int i = 0; i < nu; ++i) a += act.value2(i, u[i] - C.d()[i]);
+  } else if (force_cost(C.type())) {
+    return 0.;
+  } else if (C.type() == C_COM_POSITION) {
+    double c[3];
+    com_value(b, V, c);
+    for (int i = 0; i < 3; ++i) a += act.value2(i, c[i] - C.d()[i]);
+  } else if (C.type() == C_FRAME_VELOCITY) {
+    if (!vel) return 0.;
+    double r[6];
+    frame_velocity_res(b, V, C.d(), r);
+    for (int i = 0; i < 6; ++i) a += act.value2(i, r[i]);
+  } else {
+    double r[6] = {0., 0., 0., 0., 0., 0.};
+    const int nr = frame_residual_value(b, V, C, r);
+#pragma unroll
+    for (int i = 0; i < 6; ++i)  // fixed trip count: r stays in registers
+      if (i < nr) a += act.value2(i, r[i]);
+  }
+  return 0.5 * a;
+}
+
+// The long vector residuals (state, control) are summed lane-parallel in the calc:
+// wide_cost says which records (the first kMaxWide such records) take that path.
+constexpr int kMaxWide = 2;
+MB_HD __forceinline__ bool wide_cost(const CRec& C, int nwide) {
+  return (C.type() == C_STATE || C.type() == C_CONTROL) && nwide < kMaxWide;
+}
+// Lane l's share of twice the activation of a wide record: the rows i = l (mod L)
+// (lane 0 also the free-flyer block of a state residual, log6 of the base).
+MB_HD __forceinline__ double cost_activation_part(const Blk& b, const CRec& C, const double* x, const double* u,
+                                                  int nu, int l, int L) {
+  const Act act = cost_act(b, C, nu);
+  double a = 0.;
+  if (C.type() == C_STATE) {
+    const int ndx = 2 * b.nj, i0 = b.ff ? 6 : 0;
+    if (b.ff && l == 0) {
+      double Rr[9], pr[3], r[6];
+      ff_rel(C.d(), x, Rr, pr);
+      log6_t<double>(Rr, pr, r);
+      for (int e = 0; e < 6; ++e) a += act.value2(e, r[e]);
+    }
+    for (int i = i0 + l; i < ndx; i += L) a += act.value2(i, state_res(b, C.d(), x, i));
+  } else {
+    for (int i = l; i < nu; i += L) a += act.value2(i, u[i] - C.d()[i]);
+  }
+  return a;
+}
+
+// Cost value of the DAM (one thread; kinematics and velocities in V): sum of
+// weight * activation in record (name) order (cost-sum.hxx:89-117).
+MB_HD inline double cost_value(const Blk& b, const WVals& V, const double* x, const double* u, int nu) {
+  double total = 0.;
+  const double* cr = b.C;
+  for (int k = 0; k < b.ncost; ++k) {
+    const CRec C{cr};
+    total += C.weight() * cost_activation(b, V, C, x, u, nu);
+    cr += C.size();
+  }
+  return total;
+}
+
+// ---- contacts (ContactModel3D / 6D in the LOCAL frame) ----------------------
+// Row offset of contact record k and its record pointer.
+MB_HD inline const double* contact_rec(const Blk& b, int k, int* row0) {
+  const double* r = b.K;
+  int row = 0;
+  for (int i = 0; i < k; ++i) {
+    row += (int)r[0] == C_CONTACT_3D ? 3 : 6;
+    r += (int)r[3];
+  }
+  *row0 = row;
+  return r;
+}
+
+// a0 of a contact (contact-3d.hxx:35-43, contact-6d.hxx:31-44) in two parts,
+// so that neither holds log6 and the frame motions live at once: the
+// Baumgarte position term kp * (p - p_ref) | kp * log6(Mref^-1 oMf) (needs only
+// the placements), then the frame drift acceleration (classical for 3D, gravity
+// removed) + kd * v from the world velocity / acceleration of the body.
+MB_HD __attribute__((always_inline)) inline void contact_a0_position(const Blk& b, const WVals& W, const CRec& C, double* a0) {
+  const double kp = C.r[1];
+  double r[6] = {0., 0., 0., 0., 0., 0.};
+  if (kp != 0.) frame_residual_value(b, W, C, r);
+  const int n = C.type() == C_CONTACT_3D ? 3 : 6;
+#pragma unroll
+  for (int e = 0; e < 6; ++e)  // fixed trip count: r stays in registers
+    if (e < n) a0[e] = kp * r[e];
+}
+MB_HD __attribute__((always_inline)) inline void contact_a0_drift(const Blk& b, const WVals& W, const CRec& C, double* a0) {
+  const double* d = C.d();
+  const int j = frame_dof(b, d);
+  double Rf[9], pf[3], m6[6], vf[6], af[6];
+  frame_placement(b, W, d, Rf, pf);
+  for (int e = 0; e < 6; ++e) m6[e] = W.v(j)[e];
+  motion_act_inv(Rf, pf, m6, vf);
+  for (int e = 0; e < 6; ++e) m6[e] = W.a(j)[e] - W.root_a()[e];  // data.a has no gravity
+  motion_act_inv(Rf, pf, m6, af);
+  const double kd = C.r[2];
+  if (C.type() == C_CONTACT_3D) {
+    double wxv[3];
+    cross3(vf + 3, vf, wxv);
+    for (int e = 0; e < 3; ++e) a0[e] += af[e] + wxv[e] + kd * vf[e];
+  } else {
+    for (int e = 0; e < 6; ++e) a0[e] += af[e] + kd * vf[e];
+  }
+}
+
+// World force (at the origin) of contact record C for the multipliers lam
+// (updateForce: jMf.act(Force(lambda[, 0])), contact-3d.hxx:59-67).
+MB_HD inline void contact_world_force(const Blk& b, const WVals& W, const CRec& C, const double* lam, double* o) {
+  double Rf[9], pf[3], f[6];
+  frame_placement(b, W, C.d(), Rf, pf);
+  const bool c3 = C.type() == C_CONTACT_3D;
+  for (int e = 0; e < 6; ++e) f[e] = (c3 && e >= 3) ? 0. : lam[e];
+  force_act(Rf, pf, f, o);
+}
+
+// lane j < nj: sum of the contact forces acting on dof j's body (world) into fx[6j..]
+MB_HD inline void contact_joint_forces(const Blk& b, const WVals& W, const double* lam, double* fx, int j) {
+  double F[6] = {0., 0., 0., 0., 0., 0.};
+  const double* r = b.K;
+  int row = 0;
+  for (int k = 0; k < b.ncon; ++k) {
+    const CRec C{r};
+    if (frame_dof(b, C.d()) == j) {
+      double o[6];
+      contact_world_force(b, W, C, lam + row, o);
+      for (int e = 0; e < 6; ++e) F[e] += o[e];
+    }
+    row += C.type() == C_CONTACT_3D ? 3 : 6;
+    r += C.size();
+  }
+  for (int e = 0; e < 6; ++e) fx[6 * j + e] = F[e];
+}
+
+// lane c < nj: column c of the stacked contact Jacobian Jc (nc x nj,
+// Jc[row * nj + c]) — the LOCAL frame Jacobian (pinocchio getFrameJacobian LOCAL,
+// contact-3d.hxx:29 / contact-6d.hxx:29): the world motion S_c moved to the frame
+// (SE3::actInv of oMf), zero unless c moves the frame's body; with At != null also
+// into the columns [nj + row] of A (ld lda).
+MB_HD __attribute__((always_inline)) inline void contact_jac_lane(const Blk& b, const WVals& W, int c, double* Jc, double* At,
+                                                      int lda = 0) {
+  double Sc[6];
+  for (int e = 0; e < 6; ++e) Sc[e] = W.S(c)[e];
+  const double* r = b.K;
+  int row = 0;
+  for (int k = 0; k < b.ncon; ++k) {
+    const CRec C{r};
+    const int j = frame_dof(b, C.d());
+    double o[6] = {0., 0., 0., 0., 0., 0.};
+    if ((*W.anc(j) >> c) & 1ull) {
+      double Rf[9], pf[3];
+      frame_placement(b, W, C.d(), Rf, pf);
+      motion_act_inv(Rf, pf, Sc, o);
+    }
+    const int n = C.type() == C_CONTACT_3D ? 3 : 6;
+    for (int e = 0; e < n; ++e) {
+      Jc[(int64_t)(row + e) * b.nj + c] = o[e];
+      if (At) At[(int64_t)(b.nj + row + e) * lda + c] = o[e];
+    }
+    row += n;
+    r += C.size();
+  }
+}
+
+}  // namespace mb
+}  // namespace fddp

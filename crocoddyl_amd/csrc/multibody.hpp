@@ -28,2128 +28,30 @@
 //     Jexp6 / Jlog6 columns in dual numbers, Ad(exp6(dq)^-1) (pinocchio's
 //     SpecialEuclideanOperationTpl<3>).
 // Parameter-block layout: include/fddp_hip.h (FDDP_KNOT_EULER_FREEFWD).
+//
+// The first sections are headers of their own, each of which compiles alone, included below
+// in the order of their definitions; the later sections follow in this file:
+//   mb_base.hpp     diagnostic hooks, stores / LDS accessors, constants, Blk and its parsers
+//   mb_spatial.hpp  3-vectors, rotations, spatial algebra, joint records, quaternions
+//   mb_solve.hpp    DevExec / HostExec, Gauss-Jordan family, gj_mfma, mb_solve, mb_invert
+//   mb_se3.hpp      Dual, exp6 / log6, ff_integrate / ff_difference, Jexp6 / Jlog6 columns
+//   mb_world.hpp    WVals, the world-value and RNEA / CRBA recursions
+//   mb_costs.hpp    CRec, Act, residuals and activations, cost counting, contacts
+//   (here)          mb_mfma and the tree-sparse LTDL; world_kinematics, world_rnea, euler_step
+//                   and the knot calcs; the calcDiff: its derivation and LDS plan (DiffLayout,
+//                   diff_layout, diff_spill and their check), the per-lane derivative pieces,
+//                   the matrix-core products, knot_calc_diff_x / knot_calc_diff
 #pragma once
 
-#include <type_traits>
-
-#include "fddp_device.hpp"
-
-// Everything except the workgroup drivers (knot_calc, knot_calc_diff,
-// gauss_jordan) is __host__ __device__, so the same arithmetic is unit-tested
-// on the CPU against the oracle (tests/test_multibody_host.py).
-#define MB_HD __host__ __device__
-#ifndef MB_DUMP
-// (tools/mb_probe: copies an LDS matrix, rows x cols at leading dimension ld, out of
-// the calcDiff for the parity diagnosis; every thread calls it between phases)
-#define MB_DUMP(slot, ptr, rows, cols, ld)
-#endif
-
-// On the device every multibody record (parameter block) and the work area live in
-// LDS; the record / work-area accessors re-assert it where the pointer is formed, so
-// the accesses compile to ds_* even where the address-space inference loses the
-// entry's assumption (flat accesses to LDS pay a full round trip each). The host
-// emulation (tests/cpp/mb_host.cpp) reads ordinary memory.
-// A store to the caller's output blocks, which are in HBM: through a global pointer,
-// so the compiler emits global_store instead of a flat store that every later LDS
-// access of the wave must wait behind (flat may alias LDS).
-MB_HD __forceinline__ void mb_gstore(double* p, double v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  *(__attribute__((address_space(1))) double*)p = v;
-#else
-  *p = v;
-#endif
-}
-// two consecutive doubles (16-B aligned) in one store
-MB_HD __forceinline__ void mb_gstore2(double* p, double v0, double v1) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  *(__attribute__((address_space(1))) double2*)p = make_double2(v0, v1);
-#else
-  p[0] = v0;
-  p[1] = v1;
-#endif
-}
-// A fresh register copy of v (device: an empty asm the optimiser cannot see through), so
-// a value live across the whole kernel is reloaded from its spill slot once, here.
-template <class T>
-MB_HD __forceinline__ T mb_launder(T v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  if constexpr (sizeof(T) == 8) {
-    long long x;
-    __builtin_memcpy(&x, &v, 8);
-    asm volatile("" : "+v"(x));
-    __builtin_memcpy(&v, &x, 8);
-  } else {
-    int x;
-    __builtin_memcpy(&x, &v, 4);
-    asm volatile("" : "+v"(x));
-    __builtin_memcpy(&v, &x, 4);
-  }
-#endif
-  return v;
-}
-template <class T>
-MB_HD __forceinline__ T* mb_lds(T* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return ::fddp::lds_ptr(p);
-#else
-  return p;
-#endif
-}
-
-// MB_LANE_OPAQUE (per kernel object): every phase of the device executor gets its lane index
-// as a fresh register copy, so what a phase derives from it (addresses, lane masks) is formed
-// in the phase and not hoisted out of the caller's knot loop, to be held across every other
-// phase at the register cap.
-#ifndef MB_LANE_OPAQUE
-#define MB_LANE_OPAQUE 0
-#endif
+#include "mb_base.hpp"
+#include "mb_spatial.hpp"
+#include "mb_solve.hpp"
+#include "mb_se3.hpp"
+#include "mb_world.hpp"
+#include "mb_costs.hpp"
 
 namespace fddp {
 namespace mb {
-
-typedef unsigned long long Mask;  // one bit per dof
-constexpr int kMaxJ = 64;         // dofs (nv)
-constexpr int kJRec = 27;         // doubles per joint record
-constexpr int kCHdr = 4;          // doubles of a cost record's header
-constexpr int kMaxJacCosts = 8;   // costs with a dense residual Jacobian (frame, CoM, free-flyer state)
-constexpr int kMaxNc = 24;        // stacked contact rows (FDDP_KNOT_EULER_CONTACTFWD)
-constexpr int kMbDiffNT = 256;    // threads of the knot-parallel calcDiff workgroup
-enum { J_REVOLUTE = 0, J_FREEFLYER = 1 };
-// Cost record types; contact records (after the costs) use 5 / 6 and the same
-// frame payload as the frame costs, so frame_residual serves both.
-enum {
-  C_STATE = 1,
-  C_CONTROL = 2,
-  C_FRAME_PLACEMENT = 3,
-  C_FRAME_TRANSLATION = 4,
-  C_CONTACT_3D = 5,
-  C_CONTACT_6D = 6,
-  C_CONTACT_FORCE = 7,  // cost on a contact's force: payload [row0, nr, fref(6)] (contact-force.hxx)
-  C_COM_POSITION = 8,   // r = com(q) - cref: payload [cref(3)] (com-position.hxx:49-75)
-  C_FRICTION_CONE = 9,  // r = A lambda_lin: payload [row0, nc, nr, A (nr x 3 row-major)]
-                        // (contact-friction-cone.hxx:51-91)
-  C_FRAME_VELOCITY = 10  // r = LOCAL frame velocity - vref: frame payload + vref(6) (frame-velocity.hxx:53-84)
-};
-// Activation of a cost record: header slot 2 (core/activations/*.hpp)
-enum { A_QUAD = 0, A_WEIGHTED_QUAD = 1, A_QUAD_BARRIER = 2, A_WEIGHTED_QUAD_BARRIER = 3 };
-constexpr int kInactiveForceRow = -2;  // contact-force cost on an inactive contact: lambda = 0, no Jacobians
-
-struct Blk {
-  double dt;
-  int nj;   // nv: dofs
-  int nq;   // nv + 1 with a free-flyer root
-  int nb;   // joint records (pinocchio joints)
-  bool ff;  // record 0 is a free-flyer (dofs 0..5: base twist, body on dof 5)
-  int ncost;
-  const double* g;    // gravity (3)
-  const double* arm;  // armature (nv)
-  const double* J;    // joint records
-  const double* C;    // cost records
-  // contact section (DifferentialActionModelContactFwdDynamics); ncon == 0 without
-  int nun;            // leading unactuated dofs: tau = [0_nun; u], nu = nj - nun
-  int ncon, nc;       // active contact records, stacked rows
-  double damping;     // JMinvJt_damping
-  const double* K;    // contact records
-  // impulse section instead (ActionModelImpulseFwdDynamics, nu = 0)
-  bool impulse;
-  double r_coeff;     // restitution coefficient
-  bool enable_force;  // contact section flag 2: force Jacobians for CostModelContactForce
-};
-
-MB_HD inline Blk parse(const double* P) {
-  Blk b;
-  b.dt = P[0];
-  b.nj = (int)P[1];
-  b.ncost = (int)P[2];
-  b.g = P + FDDP_PARAM_HEADER;
-  b.arm = b.g + 3;
-  b.J = b.arm + b.nj;
-  b.ff = (int)b.J[0] == J_FREEFLYER;
-  b.nb = b.ff ? b.nj - 5 : b.nj;
-  b.nq = b.ff ? b.nj + 1 : b.nj;
-  b.C = b.J + (int64_t)kJRec * b.nb;
-  const double* e = b.C;
-  for (int k = 0; k < b.ncost; ++k) e += (int)e[3];
-  b.nun = 0;
-  b.ncon = b.nc = 0;
-  b.damping = 0.;
-  b.K = e;
-  b.impulse = false;
-  b.enable_force = false;
-  b.r_coeff = 0.;
-  if (e - P < (int64_t)P[3]) {  // [nun | r_coeff, damping, ncontact, 0 | 1 | 2] + records
-    b.impulse = (int)e[3] == 1;
-    b.enable_force = (int)e[3] == 2;
-    b.nun = b.impulse ? b.nj : (int)e[0];
-    b.r_coeff = b.impulse ? e[0] : 0.;
-    b.damping = e[1];
-    b.ncon = (int)e[2];
-    b.K = e + 4;
-    const double* r = b.K;
-    for (int k = 0; k < b.ncon; ++k) {
-      b.nc += (int)r[0] == C_CONTACT_3D ? 3 : 6;
-      r += (int)r[3];
-    }
-  }
-  return b;
-}
-
-// MB_BLK_UNIFORM (per kernel object, as MB_MFMA_SCALAR_SHAPE): the header parsed from the
-// LDS-staged block is the same in every lane, but arrives in vector registers and stays live
-// through the whole calc. parse_uniform moves every field into scalar registers (the first
-// lane's value; doubles in two halves, the LDS pointers by their 32-bit LDS address, so they
-// keep their address space). The host path is parse itself.
-#ifndef MB_BLK_UNIFORM
-#define MB_BLK_UNIFORM 0
-#endif
-#if MB_BLK_UNIFORM && defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ int mb_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ bool mb_uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
-__device__ __forceinline__ double mb_uniform(double v) {
-  int h[2];
-  __builtin_memcpy(h, &v, 8);
-  h[0] = __builtin_amdgcn_readfirstlane(h[0]);
-  h[1] = __builtin_amdgcn_readfirstlane(h[1]);
-  __builtin_memcpy(&v, h, 8);
-  return v;
-}
-__device__ __forceinline__ const double* mb_uniform(const double* p) {
-  typedef const __attribute__((address_space(3))) double* LdsP;
-  const unsigned a = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(LdsP)p);
-  return (const double*)(LdsP)(size_t)a;
-}
-#endif
-// P: the block in LDS (device)
-MB_HD __forceinline__ Blk parse_uniform(const double* P) {
-  Blk b = parse(P);
-#if MB_BLK_UNIFORM && defined(__HIP_DEVICE_COMPILE__)
-  b.dt = mb_uniform(b.dt);
-  b.nj = mb_uniform(b.nj);
-  b.nq = mb_uniform(b.nq);
-  b.nb = mb_uniform(b.nb);
-  b.ff = mb_uniform(b.ff);
-  b.ncost = mb_uniform(b.ncost);
-  b.g = mb_uniform(b.g);
-  b.arm = mb_uniform(b.arm);
-  b.J = mb_uniform(b.J);
-  b.C = mb_uniform(b.C);
-  b.nun = mb_uniform(b.nun);
-  b.ncon = mb_uniform(b.ncon);
-  b.nc = mb_uniform(b.nc);
-  b.damping = mb_uniform(b.damping);
-  b.K = mb_uniform(b.K);
-  b.impulse = mb_uniform(b.impulse);
-  b.r_coeff = mb_uniform(b.r_coeff);
-  b.enable_force = mb_uniform(b.enable_force);
-#endif
-  return b;
-}
-
-// ---- 3-vectors / rotations (column-major 3x3: R[c*3 + r]) ------------------
-MB_HD __forceinline__ void cross3(const double* a, const double* b, double* o) {
-  const double x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
-  o[0] = x;
-  o[1] = y;
-  o[2] = z;
-}
-MB_HD __forceinline__ double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-MB_HD __forceinline__ void matvec3(const double* R, const double* v, double* o) {  // o = R v
-  const double x = R[0] * v[0] + R[3] * v[1] + R[6] * v[2];
-  const double y = R[1] * v[0] + R[4] * v[1] + R[7] * v[2];
-  const double z = R[2] * v[0] + R[5] * v[1] + R[8] * v[2];
-  o[0] = x;
-  o[1] = y;
-  o[2] = z;
-}
-MB_HD __forceinline__ void matTvec3(const double* R, const double* v, double* o) {  // o = R^T v
-  const double x = R[0] * v[0] + R[1] * v[1] + R[2] * v[2];
-  const double y = R[3] * v[0] + R[4] * v[1] + R[5] * v[2];
-  const double z = R[6] * v[0] + R[7] * v[1] + R[8] * v[2];
-  o[0] = x;
-  o[1] = y;
-  o[2] = z;
-}
-MB_HD __forceinline__ void matmul3(const double* A, const double* B, double* O) {  // O = A B
-  for (int c = 0; c < 3; ++c) matvec3(A, B + 3 * c, O + 3 * c);
-}
-MB_HD __forceinline__ void matTmul3(const double* A, const double* B, double* O) {  // O = A^T B
-  for (int c = 0; c < 3; ++c) matTvec3(A, B + 3 * c, O + 3 * c);
-}
-
-// Spatial algebra in (linear, angular) order, as Pinocchio's Motion / Force.
-// actInv on a motion by M = (R, p): lin' = R^T (v - p x w), ang' = R^T w.
-MB_HD __forceinline__ void motion_act_inv(const double* R, const double* p, const double* m, double* o) {
-  double t[3];
-  cross3(p, m + 3, t);
-  t[0] = m[0] - t[0];
-  t[1] = m[1] - t[1];
-  t[2] = m[2] - t[2];
-  matTvec3(R, t, o);
-  matTvec3(R, m + 3, o + 3);
-}
-// act on a force (child -> parent): f' = R f, n' = R n + p x f'.
-MB_HD __forceinline__ void force_act(const double* R, const double* p, const double* f, double* o) {
-  double ff[3], nn[3], t[3];
-  matvec3(R, f, ff);
-  matvec3(R, f + 3, nn);
-  cross3(p, ff, t);
-  o[0] = ff[0];
-  o[1] = ff[1];
-  o[2] = ff[2];
-  o[3] = nn[0] + t[0];
-  o[4] = nn[1] + t[1];
-  o[5] = nn[2] + t[2];
-}
-// m1 x_motion m2 = (w1 x v2 + v1 x w2, w1 x w2)
-MB_HD __forceinline__ void cross_m(const double* m1, const double* m2, double* o) {
-  double a[3], b[3], c[3];
-  cross3(m1 + 3, m2, a);
-  cross3(m1, m2 + 3, b);
-  cross3(m1 + 3, m2 + 3, c);
-  o[0] = a[0] + b[0];
-  o[1] = a[1] + b[1];
-  o[2] = a[2] + b[2];
-  o[3] = c[0];
-  o[4] = c[1];
-  o[5] = c[2];
-}
-// m x_force f = (w x f, w x n + v x f)
-MB_HD __forceinline__ void cross_f(const double* m, const double* f, double* o) {
-  double a[3], b[3], c[3];
-  cross3(m + 3, f, a);
-  cross3(m + 3, f + 3, b);
-  cross3(m, f, c);
-  o[0] = a[0];
-  o[1] = a[1];
-  o[2] = a[2];
-  o[3] = b[0] + c[0];
-  o[4] = b[1] + c[1];
-  o[5] = b[2] + c[2];
-}
-// Inertia (mass m, CoM c, rotational inertia Ic about the CoM: xx yy zz xy xz yz)
-// times a motion: f = m (v - c x w), n = Ic w + c x f.
-MB_HD __forceinline__ void inertia_mul(double m, const double* c, const double* I6, const double* mo, double* o) {
-  double t[3];
-  cross3(c, mo + 3, t);
-  const double f0 = m * (mo[0] - t[0]), f1 = m * (mo[1] - t[1]), f2 = m * (mo[2] - t[2]);
-  const double w0 = mo[3], w1 = mo[4], w2 = mo[5];
-  const double n0 = I6[0] * w0 + I6[3] * w1 + I6[4] * w2;
-  const double n1 = I6[3] * w0 + I6[1] * w1 + I6[5] * w2;
-  const double n2 = I6[4] * w0 + I6[5] * w1 + I6[2] * w2;
-  const double f[3] = {f0, f1, f2};
-  cross3(c, f, t);
-  o[0] = f0;
-  o[1] = f1;
-  o[2] = f2;
-  o[3] = n0 + t[0];
-  o[4] = n1 + t[1];
-  o[5] = n2 + t[2];
-}
-MB_HD __forceinline__ double dot6(const double* a, const double* b) {
-  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3] + a[4] * b[4] + a[5] * b[5];
-}
-
-// Joint record accessors: [type, parent record (-1 universe), axis(3), placement
-// R(9) p(3), mass, CoM(3), I(6)]
-struct JRec {
-  const double* r;
-  MB_HD JRec(const Blk& b, int i) : r(mb_lds(b.J + (int64_t)kJRec * i)) {}
-  MB_HD int type() const { return (int)r[0]; }
-  MB_HD int parent() const { return (int)r[1]; }
-  MB_HD const double* axis() const { return r + 2; }
-  MB_HD const double* Rpl() const { return r + 5; }
-  MB_HD const double* ppl() const { return r + 14; }
-  MB_HD double mass() const { return r[17]; }
-  MB_HD const double* com() const { return r + 18; }
-  MB_HD const double* I6() const { return r + 21; }
-};
-
-// ---- dofs and bodies --------------------------------------------------------
-// Dof d is one lane. A free-flyer record expands into dofs 0..5 (base twist:
-// linear 0..2 along, angular 3..5 about the base axes) that share one body, whose
-// inertia sits on dof 5; placements compose along 0 -> 1 -> .. -> 5 with the base
-// pose on dof 0 and identities after it. Every other record is one revolute dof.
-MB_HD __forceinline__ int rec_of(const Blk& b, int d) { return b.ff ? (d < 6 ? 0 : d - 5) : d; }
-// the dof that carries record r's body (and its frames)
-MB_HD __forceinline__ int dof_of_rec(const Blk& b, int r) { return b.ff ? (r == 0 ? 5 : r + 5) : r; }
-// configuration index of a revolute dof
-MB_HD __forceinline__ int qof(const Blk& b, int d) { return b.ff ? d + 1 : d; }
-// the dof carrying the parent body (-1: universe)
-MB_HD __forceinline__ int body_parent(const Blk& b, int d) {
-  if (b.ff && d < 6) return -1;
-  const int pr = JRec(b, rec_of(b, d)).parent();
-  return pr < 0 ? -1 : dof_of_rec(b, pr);
-}
-// placement composition parent (free-flyer dofs chain 0 -> 5)
-MB_HD __forceinline__ int chain_parent(const Blk& b, int d) { return (b.ff && d < 6) ? d - 1 : body_parent(b, d); }
-MB_HD __forceinline__ Mask own_mask(const Blk& b, int d) { return (b.ff && d < 6) ? Mask(0x3F) : (Mask(1) << d); }
-// dofs whose body is an ancestor-or-self of d's body
-MB_HD inline Mask anc_mask(const Blk& b, int d) {
-  Mask m = own_mask(b, d);
-  for (int k = body_parent(b, d); k >= 0; k = body_parent(b, k)) m |= own_mask(b, k);
-  return m;
-}
-MB_HD __forceinline__ bool carries_body(const Blk& b, int d) { return !(b.ff && d < 5); }
-// joint-frame axis of dof d; prismatic: translation along it (free-flyer 0..2)
-MB_HD __forceinline__ bool dof_prismatic(const Blk& b, int d) { return b.ff && d < 3; }
-MB_HD __forceinline__ void dof_axis(const Blk& b, int d, double* ax) {
-  if (b.ff && d < 6) {
-    ax[0] = d % 3 == 0 ? 1. : 0.;
-    ax[1] = d % 3 == 1 ? 1. : 0.;
-    ax[2] = d % 3 == 2 ? 1. : 0.;
-  } else {
-    const double* a = JRec(b, rec_of(b, d)).axis();
-    ax[0] = a[0];
-    ax[1] = a[1];
-    ax[2] = a[2];
-  }
-}
-
-// R = Rpl * exp(q [axis]x)  (Rodrigues: c I + s [a]x + (1 - c) a a^T)
-MB_HD inline void joint_rotation(const double* Rpl, const double* ax, double q, double* R) {
-  double s, c;
-  sincos(q, &s, &c);
-  const double oc = 1. - c;
-  double Rj[9];
-  Rj[0] = c + oc * ax[0] * ax[0];
-  Rj[1] = oc * ax[1] * ax[0] + s * ax[2];
-  Rj[2] = oc * ax[2] * ax[0] - s * ax[1];
-  Rj[3] = oc * ax[0] * ax[1] - s * ax[2];
-  Rj[4] = c + oc * ax[1] * ax[1];
-  Rj[5] = oc * ax[2] * ax[1] + s * ax[0];
-  Rj[6] = oc * ax[0] * ax[2] + s * ax[1];
-  Rj[7] = oc * ax[1] * ax[2] - s * ax[0];
-  Rj[8] = c + oc * ax[2] * ax[2];
-  matmul3(Rpl, Rj, R);
-}
-
-// Eigen QuaternionBase::toRotationMatrix, quaternion (x, y, z, w); column-major R
-MB_HD inline void quat_to_R(const double* qv, double* R) {
-  const double x = qv[0], y = qv[1], z = qv[2], w = qv[3];
-  const double tx = 2. * x, ty = 2. * y, tz = 2. * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w;
-  const double txx = tx * x, txy = ty * x, txz = tz * x;
-  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1. - (tyy + tzz);
-  R[1] = txy + twz;
-  R[2] = txz - twy;
-  R[3] = txy - twz;
-  R[4] = 1. - (txx + tzz);
-  R[5] = tyz + twx;
-  R[6] = txz + twy;
-  R[7] = tyz - twx;
-  R[8] = 1. - (txx + tyy);
-}
-
-// Eigen's quaternion from a rotation matrix (quaternionbase_assign_impl), with the
-// index selection written as explicit selects (no runtime-indexed arrays).
-MB_HD inline void R_to_quat(const double* R, double* q) {
-  auto at = [&](int r, int c) { return R[c * 3 + r]; };
-  const double t = at(0, 0) + at(1, 1) + at(2, 2);
-  if (t > 0.) {
-    double s = sqrt(t + 1.);
-    q[3] = 0.5 * s;
-    s = 0.5 / s;
-    q[0] = (at(2, 1) - at(1, 2)) * s;
-    q[1] = (at(0, 2) - at(2, 0)) * s;
-    q[2] = (at(1, 0) - at(0, 1)) * s;
-    return;
-  }
-  int i = 0;
-  if (at(1, 1) > at(0, 0)) i = 1;
-  if (at(2, 2) > (i == 0 ? at(0, 0) : at(1, 1))) i = 2;
-  if (i == 0) {
-    double s = sqrt(at(0, 0) - at(1, 1) - at(2, 2) + 1.);
-    q[0] = 0.5 * s;
-    s = 0.5 / s;
-    q[3] = (at(2, 1) - at(1, 2)) * s;
-    q[1] = (at(1, 0) + at(0, 1)) * s;
-    q[2] = (at(2, 0) + at(0, 2)) * s;
-  } else if (i == 1) {
-    double s = sqrt(at(1, 1) - at(2, 2) - at(0, 0) + 1.);
-    q[1] = 0.5 * s;
-    s = 0.5 / s;
-    q[3] = (at(0, 2) - at(2, 0)) * s;
-    q[2] = (at(2, 1) + at(1, 2)) * s;
-    q[0] = (at(0, 1) + at(1, 0)) * s;
-  } else {
-    double s = sqrt(at(2, 2) - at(0, 0) - at(1, 1) + 1.);
-    q[2] = 0.5 * s;
-    s = 0.5 / s;
-    q[3] = (at(1, 0) - at(0, 1)) * s;
-    q[0] = (at(0, 2) + at(2, 0)) * s;
-    q[1] = (at(1, 2) + at(2, 1)) * s;
-  }
-}
-
-// Phase executor: run(f) calls f(lane) for every thread of the workgroup and
-// then synchronises (device), or for lanes 0..nt-1 in order (host emulation,
-// tests/test_multibody_host.py). Within one phase no lane reads what another
-// lane writes, so both orders give the same result. run_w0(f): a phase only
-// wave 0 works in, closed by a wave-level fence instead of a workgroup barrier
-// (the other waves skip ahead to the next sync()); sync(): the barrier that
-// hands wave-0 results back to the whole workgroup.
-// Everything the device executor runs is inlined into the kernel: LDS pointers
-// keep their address space only through inlining (an outlined phase or helper
-// takes them as generic pointers and reaches LDS with flat instructions, at
-// global-memory latency).
-struct DevExec {
-  int nt;
-  template <class F>
-  __device__ __forceinline__ void run(F f) const {
-#if MB_LANE_OPAQUE
-    [[clang::always_inline]] f(mb_launder((int)threadIdx.x));
-#else
-    [[clang::always_inline]] f((int)threadIdx.x);
-#endif
-    __syncthreads();
-  }
-  template <class F>
-  __device__ __forceinline__ void run_w0(F f) const {
-    if (threadIdx.x < 64) {
-      [[clang::always_inline]] f((int)threadIdx.x);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-  }
-  __device__ void sync() const { __syncthreads(); }
-  // an LDS pointer re-typed through the LDS address space (fddp_device.hpp lds_ptr)
-  template <class T>
-  __device__ __forceinline__ T* lds(T* p) const {
-    return lds_ptr(p);
-  }
-};
-struct HostExec {
-  int nt;
-  template <class F>
-  void run(F f) const {
-    for (int l = 0; l < nt; ++l) f(l);
-  }
-  template <class F>
-  void run_w0(F f) const {
-    for (int l = 0; l < 64 && l < nt; ++l) f(l);
-  }
-  void sync() const {}
-  template <class T>
-  T* lds(T* p) const {
-    return p;
-  }
-};
-
-// Gauss-Jordan on the column-major nr x nc matrix A (ld nr) without pivoting
-// (the left nr x nr block is SPD): one column per lane (lane < nc), one pivot
-// per phase; the left block's pivot column is only read in its step. Returns
-// false if a pivot is not positive. Columns beyond 64 are taken by the same
-// lanes in a second pass of each pivot step.
-// Runs on wave 0 between wave-level fences; the caller's preceding phase must
-// have ended in a workgroup barrier.
-// Leading dimension of the nj-row matrices in LDS that are walked column per lane
-// (mass matrix / KKT blocks): odd, so a wave's 64 column reads hit distinct banks.
-MB_HD __forceinline__ int lda_of(int nj) { return nj | 1; }
-
-// Device version: every thread of the workgroup takes columns tid, tid + nt, ...
-// (one pass for nc <= nt), one workgroup barrier per pivot; plain arguments and no
-// lambdas, so nothing of it lives in scratch. The column update runs in chunks of 8
-// rows, loads first, so the LDS round trips overlap.
-__device__ __forceinline__ bool gauss_jordan_dev(double* A, int nr, int ld, int nc, int* flag) {
-  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-  A = lds_ptr(A);
-  flag = lds_ptr(flag);
-  __syncthreads();
-  bool bad = false;
-#pragma unroll 1
-  for (int k = 0; k < nr; ++k) {
-    const double piv = A[(int64_t)k * ld + k];
-    bad = bad || !(piv > 0.);
-    const double* pc = A + (int64_t)k * ld;
-#pragma unroll 1
-    for (int cc = tid; cc < nc; cc += nt) {
-      if (cc <= k || bad) continue;
-      double* col = A + (int64_t)cc * ld;
-      const double akc = col[k] / piv;
-      int r0 = 0;
-#pragma unroll 1
-      for (; r0 + 8 <= nr; r0 += 8) {
-        double pv[8], cv[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          pv[r] = pc[r0 + r];
-          cv[r] = col[r0 + r];
-        }
-#pragma unroll
-        for (int r = 0; r < 8; ++r) col[r0 + r] = (r0 + r == k) ? akc : cv[r] - pv[r] * akc;
-      }
-#pragma unroll 1
-      for (; r0 < nr; ++r0) col[r0] = (r0 == k) ? akc : col[r0] - pc[r0] * akc;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) *flag = bad ? 1 : 0;
-  __syncthreads();
-  return !bad;
-}
-
-// v from lane l (uniform l) of the wave, as a scalar
-__device__ __forceinline__ double readlane_d(double v, int l) {
-  const long long bits = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)bits, l);
-  const int hi = __builtin_amdgcn_readlane((int)(bits >> 32), l);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// Gauss-Jordan with the rows in registers: lane r of every wave holds row r
-// (nr <= 64) of the column slabs of CPW columns the wave owns (slab s of wave w:
-// columns (w + s nw) CPW ..); per pivot k the wave owning column k publishes it
-// through LDS (pb: 2 x 64 doubles, double-buffered, so one barrier per pivot), the
-// pivot row comes from lane k by readlane. The pivot loop runs in chunks of CPW
-// unrolled steps, so the owner's register of column k is static. No LDS traffic
-// beyond the one published column per pivot. Returns false if a pivot is not
-// positive (the LLT failure the reference reports).
-// id0: A's columns from id0 on start as an identity block ([M | I]); their slabs
-// are skipped until the pivot reaches them (the update is the identity there too).
-template <int CPW, int SPW>
-__device__ __forceinline__ bool gauss_jordan_rows(double* A, int nr, int ld, int nc, double* pb, int* flag,
-                                                  int id0 = 1 << 30) {
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (int)(blockDim.x >> 6);
-  const int nslab = (nc + CPW - 1) / CPW;
-  A = lds_ptr(A);
-  pb = lds_ptr(pb);
-  flag = lds_ptr(flag);
-  double v[SPW][CPW];
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < SPW; ++s) {
-    const int slab = wave + s * nw;
-#pragma unroll
-    for (int j = 0; j < CPW; ++j) {
-      const int c = slab * CPW + j;
-      v[s][j] = (lane < nr && slab < nslab && c < nc) ? A[(int64_t)c * ld + lane] : 0.;
-    }
-  }
-  bool bad = false;
-#pragma unroll 1
-  for (int kk = 0; kk < nr; kk += CPW) {
-    const int kslab = kk / CPW, owner = kslab % nw, os = kslab / nw;
-#pragma unroll
-    for (int j = 0; j < CPW; ++j) {
-      const int k = kk + j;
-      if (k >= nr) continue;  // (uniform)
-      double* pcol = pb + (k & 1) * 64;
-      if (wave == owner) {
-        double val = 0.;
-#pragma unroll
-        for (int s = 0; s < SPW; ++s)
-          if (s == os) val = v[s][j];
-        pcol[lane] = val;
-      }
-      __syncthreads();
-      const double piv = pcol[k];
-      const double ark = pcol[lane];  // A[r][k] of this lane's row
-      bad = bad || !(piv > 0.);
-      const double ipiv = 1. / piv;
-#pragma unroll
-      for (int s = 0; s < SPW; ++s) {
-        // a slab left of the pivot holds unit columns (row k zero): the update is the
-        // identity there, so it is skipped (wave-uniform)
-        const int slab = wave + s * nw;
-        if (slab >= nslab || slab * CPW + CPW <= k || slab * CPW - id0 > k) continue;
-#pragma unroll
-        for (int jj = 0; jj < CPW; ++jj) {
-          const double akc = readlane_d(v[s][jj], k) * ipiv;  // pivot row, scaled
-          v[s][jj] = lane == k ? akc : v[s][jj] - ark * akc;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < SPW; ++s) {
-    const int slab = wave + s * nw;
-#pragma unroll
-    for (int j = 0; j < CPW; ++j) {
-      const int c = slab * CPW + j;
-      if (lane < nr && slab < nslab && c < nc) A[(int64_t)c * ld + lane] = v[s][j];
-    }
-  }
-  if (tid == 0) *flag = bad ? 1 : 0;
-  __syncthreads();
-  return !bad;
-}
-
-// the device executor takes the register version when the slabs fit (overload
-// resolution prefers these to the template below, which serves the host emulation)
-// The slab count per wave follows nc (the block is uniform): every unrolled register
-// column costs a readlane pair and an FMA per pivot, so the [M | Jc^T | r] block of
-// the calc (nc = nj + nc + 1) and the small Schur block do not pay for the 3 slabs
-// per wave that the calcDiff's [M | I] needs.
-// SPW: the call site's bound on the slabs per wave (one instantiation per call site
-// keeps the register budget of the kernels it is inlined into); blocks wider than
-// SPW slabs per wave take the LDS version.
-template <int SPW>
-__device__ __forceinline__ bool gauss_jordan_regs(double* A, int nr, int ld, int nc, int* flag, double* pb,
-                                                  int id0 = 1 << 30) {
-  if (nr <= 64 && nc <= SPW * 8 * (int)(blockDim.x >> 6)) return gauss_jordan_rows<8, SPW>(A, nr, ld, nc, pb, flag, id0);
-  return gauss_jordan_dev(A, nr, ld, nc, flag);
-}
-template <int SPW>
-__device__ __forceinline__ bool gauss_jordan(const DevExec&, double* A, int nr, int ld, int nc, int* flag,
-                                             double* pb, int id0 = 1 << 30) {
-  return gauss_jordan_regs<SPW>(A, nr, ld, nc, flag, pb, id0);
-}
-
-// no side work for the idle waves of gj_mfma
-struct GjNoSide {
-  __device__ void operator()(int, int, int) const {}
-};
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MB_GJ_ROWS)
-// Blocked Gauss-Jordan on the fp64 matrix cores. A: nr x nc column-major in LDS (ld),
-// its left nr x nr block SPD. Pivot blocks of 16 rows; per block k:
-//  A  every wave inverts the diagonal block D itself, in registers (the symmetric sweep:
-//     a_pp <- -1/a_pp, a_ip <- a_ip/a_pp, a_pj <- a_pj/a_pp, a_ij <- a_ij - a_ip a_pj/a_pp;
-//     after all 16 pivots N = -D^-1), so no barrier separates it from B;
-//  B  the wave owning column tile j (j mod nw) forms R_j = N A_kj = -D^-1 A_kj and updates
-//     its whole column: A_ij += A_ik R_j (i != k), A_kj <- -R_j (v_mfma_f64_16x16x4_f64);
-//  C  (inverse) the diagonal column block, A_ik <- A_ik N, A_kk <- -N, deferred to its
-//     owner's next pass (nobody else reads it before then): one workgroup barrier per
-//     pivot block instead of one per pivot.
-// N's registers serve as both MFMA operands: lane (i = lane & 15, g = lane >> 4) holds
-// N[i][g + 4q], q = 0..3, which is the A fragment of k-chunk q (k = g + 4q) and, N being
-// symmetric, the B fragment too; R_j's accumulators are the B fragments of the update
-// with the same k order. Columns: the right-hand sides start at the 16-aligned virtual
-// column nrp (their tiles never share a tile with the matrix). The pivots are the LDL^T
-// pivots in order, so a non-positive one is the LLT failure the unblocked sweep reports.
-// inverse: the left block becomes M^-1 in place; the right-hand sides M^-1 B either way.
-#ifndef MB_GJ_MARK
-#define MB_GJ_MARK(id)  // (tools/mb_probe: phase stamps)
-#endif
-// side(slot, lane, nlanes): independent work of the caller for the waves that own no
-// column tile (wave >= nct), one slot per barrier interval (nbr + 1 of them), so the
-// latency-bound pivot chain of the owners hides it.
-template <class Side = GjNoSide>
-__device__ __forceinline__ bool gj_mfma(double* A_, int nr, int ld, int nc, bool inverse, int* flag,
-                                        Side side = Side{}) {
-  typedef __attribute__((address_space(3))) double lds_d;
-  typedef double f64x4 __attribute__((ext_vector_type(4)));
-  lds_d* A = (lds_d*)lds_ptr(A_);
-  // the shape in scalar registers (the callers read it from the LDS parameter block, i.e.
-  // into vector registers): the sweep's `r0 + p < nr` then skips the padding pivots of the
-  // last block by a scalar branch instead of running all 16 under a lane mask
-  nr = __builtin_amdgcn_readfirstlane(nr);
-  ld = __builtin_amdgcn_readfirstlane(ld);
-  nc = __builtin_amdgcn_readfirstlane(nc);
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (int)(blockDim.x >> 6);
-  const int li = lane & 15, lk = lane >> 4;
-  const int nrp = (nr + 15) & ~15, nbr = nrp >> 4, nct = (nrp + nc - nr + 15) >> 4;
-  auto phys = [&](int v) { return v < nr ? v : (v < nrp ? -1 : v - nrp + nr); };
-  // branch-free guarded load: an in-range address always, the value selected
-  auto at = [&](int r, int c) -> double {
-    const bool v = r < nr && c >= 0 && c < nc;
-    const double x = A[(v ? r : 0) + ld * (v ? c : 0)];
-    return v ? x : 0.;
-  };
-  // Without side work or the inverse's trailing column updates (mb_solve), the per-step
-  // workgroup barrier is replaced by a progress counter: step k + 1 needs tile k + 1 as
-  // updated by step k (its sweep reads the diagonal block, every wave's update its
-  // column), and nothing else another wave writes — a pivot tile is never written again
-  // once passed — so only its owner is waited for, and the other waves' updates of the
-  // later tiles overlap the next sweep.
-  constexpr bool kNoSide = std::is_same<Side, GjNoSide>::value;
-  const bool flagged = kNoSide && !inverse;
-  int* prog = flag + 1;   // diagonal block of tile k ready (its sweep may start)
-  int* prog2 = flag + 2;  // all of tile k ready (the updates may read it)
-  if (flagged && tid == 0) *prog = *prog2 = 0;
-  __syncthreads();
-  MB_GJ_MARK(0);
-  bool bad = false;
-  double Np[4] = {0., 0., 0., 0.};
-  // C: column block kc <- A_ik N (i != kc), the diagonal block <- -N
-  auto col_update = [&](int kc, const double* N) {
-    const int c = 16 * kc + li;
-#pragma unroll 1
-    for (int i = 0; i < nbr; ++i) {
-      if (i == kc) continue;
-      f64x4 acc = {0., 0., 0., 0.};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int kk = 16 * kc + lk + 4 * q;
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(at(16 * i + li, kk < nr ? kk : -1), N[q], acc, 0, 0, 0);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int r = 16 * i + lk + 4 * q;
-        if (r < nr && c < nr) A[r + ld * c] = acc[q];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int r = 16 * kc + li, cc = 16 * kc + lk + 4 * q;
-      if (r < nr && cc < nr) A[r + ld * cc] = -N[q];
-    }
-  };
-#pragma unroll 1
-  for (int k = 0; k < nbr; ++k) {
-    const int r0 = 16 * k;
-    double d[4] = {0., 0., 0., 0.};
-    if (flagged && k > 0 && wave < nct) {  // tile k updated through step k - 1
-      lds_wait_ge(prog, k);
-      asm volatile("" ::: "memory");
-    }
-    // A: only the waves that own a column tile need N (one sweep per SIMD, not two);
-    // the padding pivots beyond nr are skipped (their identity rows stay +1, which only
-    // ever multiplies the zero-loaded padding)
-    if (wave < nct) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = lk + 4 * q;
-        const double x = at(r0 + li, r0 + c < nr ? r0 + c : -1);
-        d[q] = (r0 + li < nr && r0 + c < nr) ? x : (li == c ? 1. : 0.);
-      }
-#pragma unroll
-      for (int p = 0; p < 16; ++p) {
-        if (r0 + p < nr) {  // (uniform; the loop stays fully unrolled, d[] static)
-          const int pq = p >> 2, pg = p & 3;
-          const double app = readlane_d(d[pq], p + 16 * pg);
-          const double aip = row_to_all_d(d[pq], pg);  // = __shfl(d[pq], li + 16 pg)
-          double apc[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) apc[q] = row_bcast_d(d[q], p);  // = __shfl(d[q], p + 16 lk)
-          bad = bad || !(app > 0.);
-          // 1 / app from v_rcp_f64 (relative error up to ~2^-23) corrected to working
-          // precision in three dependent fmas: with e = 1 - app x0, x0 (1 + e + e^2) has
-          // relative error e^3 (one Newton step leaves e^2 ~ 1e-14, which the contact
-          // KKT's conditioning, ~1e7, turned into 1e-7 trajectory errors). The pivot chain
-          // is latency-bound (35 cycles per dependent f64 op), so not the IEEE division's
-          // special-case scaling: app > 0 is all that is used.
-          double ip = __builtin_amdgcn_rcp(app);
-#ifdef MB_GJ_RCP_FAST
-          ip = __builtin_fma(ip, __builtin_fma(-app, ip, 1.), ip);
-#else
-          {
-            const double e = __builtin_fma(-app, ip, 1.);
-            ip = __builtin_fma(ip, __builtin_fma(e, e, e), ip);
-          }
-#endif
-          const double t = aip * ip;
-          // row p: a_pc ip; the others: a_ic - t a_pc (one fma with per-lane factors);
-          // column p (register pq of the lanes with lk == pg): t, the pivot itself -ip
-          const bool rp = li == p;
-          const double sf = rp ? ip : -t;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const double v = __builtin_fma(sf, apc[q], rp ? 0. : d[q]);
-            d[q] = (q == pq && lk == pg) ? (rp ? -ip : t) : v;
-          }
-        }
-      }
-    }
-    MB_GJ_MARK(1 + 3 * k);
-    if (flagged && k > 0 && wave < nct) {  // all of tile k updated through step k - 1
-      lds_wait_ge(prog2, k);
-      asm volatile("" ::: "memory");
-    }
-#pragma unroll 1
-    for (int j = wave; j < nct; j += nw) {
-      if (inverse && j == k - 1) col_update(j, Np);
-      if (j == k || (!inverse && j < k)) continue;
-      const int pc = phys(16 * j + li);
-      f64x4 R = {0., 0., 0., 0.};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) R = __builtin_amdgcn_mfma_f64_16x16x4f64(d[q], at(r0 + lk + 4 * q, pc), R, 0, 0, 0);
-      // row blocks from k + 1 on (rotated): the next pivot tile's diagonal block first
-#pragma unroll 1
-      for (int ii = 0; ii < nbr; ++ii) {
-        const int i = ii + k + 1 < nbr ? ii + k + 1 : ii + k + 1 - nbr;
-        if (i == k) continue;
-        f64x4 acc;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] = at(16 * i + lk + 4 * q, pc);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int kk = r0 + lk + 4 * q;
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(at(16 * i + li, kk < nr ? kk : -1), R[q], acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int r = 16 * i + lk + 4 * q;
-          if (r < nr && pc >= 0 && pc < nc) A[r + ld * pc] = acc[q];
-        }
-        if (flagged && j == k + 1 && i == k + 1) {  // the next sweep's block is ready
-          if (lane == 0) lds_publish(prog, k + 1);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int r = r0 + lk + 4 * q;
-        if (r < nr && pc >= 0 && pc < nc) A[r + ld * pc] = -R[q];
-      }
-      if (flagged && j == k + 1) {  // the whole next pivot tile is ready
-        if (lane == 0) lds_publish(prog2, k + 1);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) Np[q] = d[q];
-    if (wave >= nct) side(k, tid - 64 * nct, (nw - nct) * 64);
-    MB_GJ_MARK(2 + 3 * k);
-    if (!flagged) __syncthreads();
-    MB_GJ_MARK(3 + 3 * k);
-  }
-  if (inverse)
-    for (int j = wave; j < nct; j += nw)
-      if (j == nbr - 1) col_update(j, Np);
-  if (wave >= nct) side(nbr, tid - 64 * nct, (nw - nct) * 64);
-  if (tid == 0) *lds_ptr(flag) = bad ? 1 : 0;
-  __syncthreads();
-  MB_GJ_MARK(20);
-  return !bad;
-}
-#endif
-
-// whether mb_invert works in place (then [M | I] needs no identity half)
-__device__ __forceinline__ constexpr bool mb_inv_inplace(const DevExec&) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MB_GJ_ROWS)
-  return true;
-#else
-  return false;
-#endif
-}
-// [M | B] (nr x nc, M SPD) -> M^-1 B in the columns beyond M (the left block is consumed)
-__device__ __forceinline__ bool mb_solve(const DevExec&, double* A, int nr, int ld, int nc, int* flag, double* pb) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MB_GJ_ROWS)
-  (void)pb;
-  return gj_mfma(A, nr, ld, nc, false, flag);
-#else
-  return gauss_jordan_regs<2>(A, nr, ld, nc, flag, pb);
-#endif
-}
-// [M | I] (nr x 2 nr, M SPD) -> M^-1, at *Minv (device: in place of M). side: work the
-// idle waves run meanwhile (gj_mfma); *nslots: the slots it ran (0: none)
-template <class Side = GjNoSide>
-__device__ __forceinline__ bool mb_invert(const DevExec&, double* A, int nr, int ld, int* flag, double* pb,
-                                          double** Minv, Side side = Side{}, int* nslots = nullptr) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MB_GJ_ROWS)
-  (void)pb;
-  *Minv = A;
-  const int nbr = (nr + 15) >> 4, nw = (int)(blockDim.x >> 6);
-  if (nslots) *nslots = nw > nbr ? nbr + 1 : 0;
-  return gj_mfma(A, nr, ld, nr, true, flag, side);
-#else
-  (void)side;
-  if (nslots) *nslots = 0;
-  *Minv = A + (int64_t)ld * nr;
-  return gauss_jordan_regs<3>(A, nr, ld, 2 * nr, flag, pb, nr);
-#endif
-}
-
-template <int SPW, class X>
-MB_HD __attribute__((noinline)) bool gauss_jordan(const X& ex, double* A, int nr, int ld, int nc, int* flag,
-                                                 double* = nullptr, int = 0) {
-  ex.run_w0([&](int lane) {
-    if (lane == 0) *flag = 0;
-  });
-#pragma unroll 1
-  for (int k = 0; k < nr; ++k) {
-    ex.run_w0([&](int lane) {
-      const double piv = A[(int64_t)k * ld + k];
-      if (!(piv > 0.)) {
-        if (lane == 0) *flag = 1;
-        return;
-      }
-#pragma unroll 1
-      for (int cc = lane; cc < nc; cc += 64) {
-        if (cc <= k) continue;
-        // pivot column and own column in chunks of 8 rows through registers
-        // (independent loads, then the updates): no LDS round trip per row
-        double* col = A + (int64_t)cc * ld;
-        const double* pc = A + (int64_t)k * ld;
-        const double akc = col[k] / piv;
-#pragma unroll 1
-        for (int r0 = 0; r0 < nr; r0 += 8) {
-          double pv[8], cv[8];
-#pragma unroll
-          for (int r = 0; r < 8; ++r)
-            if (r0 + r < nr) {
-              pv[r] = pc[r0 + r];
-              cv[r] = col[r0 + r];
-            }
-#pragma unroll
-          for (int r = 0; r < 8; ++r)
-            if (r0 + r < nr) col[r0 + r] = (r0 + r == k) ? akc : cv[r] - pv[r] * akc;
-        }
-      }
-    });
-  }
-  ex.sync();
-  return *flag == 0;
-}
-// the host emulation (and any other executor): the unblocked sweep on [M | B], [M | I]
-template <class X>
-MB_HD __forceinline__ constexpr bool mb_inv_inplace(const X&) {
-  return false;
-}
-template <class X>
-MB_HD __forceinline__ bool mb_solve(const X& ex, double* A, int nr, int ld, int nc, int* flag, double* pb) {
-  return gauss_jordan<2>(ex, A, nr, ld, nc, flag, pb);
-}
-template <class X, class Side = int>
-MB_HD __forceinline__ bool mb_invert(const X& ex, double* A, int nr, int ld, int* flag, double* pb, double** Minv,
-                                     Side = Side{}, int* nslots = nullptr) {
-  if (nslots) *nslots = 0;
-  *Minv = A + (int64_t)ld * nr;
-  return gauss_jordan<3>(ex, A, nr, ld, 2 * nr, flag, pb, nr);
-}
-
-// ---- dual numbers for the exp6 / log6 Jacobians ----------------------------
-struct Dual {
-  double v, d;
-  Dual() = default;
-  MB_HD constexpr Dual(double v_, double d_ = 0.) : v(v_), d(d_) {}
-};
-MB_HD __forceinline__ Dual operator+(Dual a, Dual b) { return {a.v + b.v, a.d + b.d}; }
-MB_HD __forceinline__ Dual operator-(Dual a, Dual b) { return {a.v - b.v, a.d - b.d}; }
-MB_HD __forceinline__ Dual operator*(Dual a, Dual b) { return {a.v * b.v, a.d * b.v + a.v * b.d}; }
-MB_HD __forceinline__ Dual operator*(double s, Dual a) { return {s * a.v, s * a.d}; }
-MB_HD __forceinline__ Dual operator/(Dual a, Dual b) { return {a.v / b.v, (a.d * b.v - a.v * b.d) / (b.v * b.v)}; }
-MB_HD __forceinline__ Dual msqrt(Dual a) {
-  const double s = sqrt(a.v);
-  return {s, a.d / (2. * s)};
-}
-MB_HD __forceinline__ Dual masin(Dual a) { return {asin(a.v), a.d / sqrt(1. - a.v * a.v)}; }
-MB_HD __forceinline__ Dual macos(Dual a) { return {acos(a.v), -a.d / sqrt(1. - a.v * a.v)}; }
-MB_HD __forceinline__ Dual msin(Dual a) { return {sin(a.v), a.d * cos(a.v)}; }
-MB_HD __forceinline__ Dual mcos(Dual a) { return {cos(a.v), -a.d * sin(a.v)}; }
-MB_HD __forceinline__ double mval(Dual a) { return a.v; }
-MB_HD __forceinline__ double msqrt(double a) { return sqrt(a); }
-MB_HD __forceinline__ double masin(double a) { return asin(a); }
-MB_HD __forceinline__ double macos(double a) { return acos(a); }
-MB_HD __forceinline__ double msin(double a) { return sin(a); }
-MB_HD __forceinline__ double mcos(double a) { return cos(a); }
-MB_HD __forceinline__ double mval(double a) { return a; }
-
-// log6(R, p) -> (lin, ang) (pinocchio::log6), R column-major. T = double, or
-// Dual so that the tangent along (dR, dp) is Jlog6 * xi. Same branches as
-// oracle/multibody_np.py:log3/log6.
-template <class T>
-MB_HD inline void log6_t(const T* R, const T* p, T* out) {
-  auto at = [&](int r, int c) { return R[c * 3 + r]; };
-  const T one(1.);
-  const T tr = at(0, 0) + at(1, 1) + at(2, 2);
-  const T c = 0.5 * (tr - one);
-  const T w[3] = {at(2, 1) - at(1, 2), at(0, 2) - at(2, 0), at(1, 0) - at(0, 1)};
-  const T s2 = 0.25 * (w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-  T om[3];
-  T sth = T(0.), thg = T(0.);  // sin(theta), theta of the generic branch (beta reuses them)
-  bool generic = false;
-  if (mval(s2) < 1e-8 && mval(c) > 0.) {
-    const T k = 0.5 * (one + (1. / 6.) * s2 + (3. / 40.) * (s2 * s2) + (5. / 112.) * (s2 * s2 * s2));
-    for (int e = 0; e < 3; ++e) om[e] = k * w[e];
-  } else if (mval(s2) < 1e-8) {  // theta near pi: axis from the symmetric part (value only)
-    // (explicit selects: no runtime-indexed arrays, which would live in scratch)
-    const double cv = mval(c) < -1. ? -1. : mval(c);
-    const double th = acos(cv);
-    auto axc = [&](double d) {
-      const double t = (d - cv) / (1. - cv);
-      return t > 0. ? sqrt(t) : 0.;
-    };
-    const double a0 = axc(mval(at(0, 0))), a1 = axc(mval(at(1, 1))), a2 = axc(mval(at(2, 2)));
-    const int i0 = (a1 > a0) ? ((a2 > a1) ? 2 : 1) : ((a2 > a0) ? 2 : 0);
-    const double s01 = mval(at(0, 1)) + mval(at(1, 0)), s02 = mval(at(0, 2)) + mval(at(2, 0)),
-                 s12 = mval(at(1, 2)) + mval(at(2, 1));
-    auto sgn = [](double v) { return v >= 0. ? 1. : -1.; };
-    const double g0 = i0 == 0 ? 1. : (i0 == 1 ? sgn(s01) : sgn(s02));
-    const double g1 = i0 == 1 ? 1. : (i0 == 0 ? sgn(s01) : sgn(s12));
-    const double g2 = i0 == 2 ? 1. : (i0 == 0 ? sgn(s02) : sgn(s12));
-    const double wi = i0 == 0 ? mval(w[0]) : (i0 == 1 ? mval(w[1]) : mval(w[2]));
-    const double flip = wi < 0. ? -th : th;
-    om[0] = T(flip * g0 * a0);
-    om[1] = T(flip * g1 * a1);
-    om[2] = T(flip * g2 * a2);
-  } else {
-    const T s = msqrt(s2);
-    T th;
-    if (mval(c) > 0.5)
-      th = masin(s);
-    else if (mval(c) < -0.5)
-      th = T(M_PI) - masin(s);
-    else
-      th = macos(c);
-    const T k = th / (2. * s);
-    for (int e = 0; e < 3; ++e) om[e] = k * w[e];
-    sth = s;
-    thg = th;
-    generic = true;
-  }
-  const T t2 = om[0] * om[0] + om[1] * om[1] + om[2] * om[2];
-  T beta;
-  if (mval(t2) < 1e-2) {
-    beta = T(1. / 12.) + (1. / 720.) * t2 + (1. / 30240.) * (t2 * t2) + (1. / 1209600.) * (t2 * t2 * t2);
-  } else if (generic) {  // 1/t^2 - sin t / (2 t (1 - cos t)) with sin, cos of theta read off R
-    beta = one / (thg * thg) - sth / (2. * thg * (one - c));
-  } else {
-    const T t = msqrt(t2);
-    beta = one / t2 - msin(t) / (2. * t * (one - mcos(t)));
-  }
-  // v = (I - 0.5 [w]x + beta [w]x^2) p ; [w]x^2 p = w (w.p) - |w|^2 p
-  const T wp = om[0] * p[0] + om[1] * p[1] + om[2] * p[2];
-  const T wxp[3] = {om[1] * p[2] - om[2] * p[1], om[2] * p[0] - om[0] * p[2], om[0] * p[1] - om[1] * p[0]};
-  for (int e = 0; e < 3; ++e) {
-    const T w2p = om[e] * wp - t2 * p[e];
-    out[e] = p[e] - 0.5 * wxp[e] + beta * w2p;
-    out[3 + e] = om[e];
-  }
-}
-
-// exp6(nu) -> (R, p) (pinocchio::exp6): R = cos t I + (1 - cos t)/t^2 w w^T +
-// sin t / t [w]x, p = sin t / t v + (1 - sin t / t)/t^2 (w.v) w + (1 - cos t)/t^2 w x v,
-// Taylor branch for t^2 < 1e-8 (as oracle/multibody_np.py:exp6). T = double or Dual.
-template <class T>
-MB_HD inline void exp6_t(const T* nu, T* R, T* p) {
-  const T* v = nu;
-  const T* w = nu + 3;
-  const T t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  T ct, st_t, a_wxv, a_w;
-  if (mval(t2) < 1e-8) {
-    ct = T(1.) - 0.5 * t2 + (1. / 24.) * (t2 * t2);
-    st_t = T(1.) - (1. / 6.) * t2 + (1. / 120.) * (t2 * t2);
-    a_wxv = T(0.5) - (1. / 24.) * t2 + (1. / 720.) * (t2 * t2);
-    a_w = T(1. / 6.) - (1. / 120.) * t2 + (1. / 5040.) * (t2 * t2);
-  } else {
-    const T t = msqrt(t2);
-    ct = mcos(t);
-    st_t = msin(t) / t;
-    a_wxv = (T(1.) - ct) / t2;
-    a_w = (T(1.) - st_t) / t2;
-  }
-  // column-major R[c*3 + r] = ct d_rc + a_wxv w_r w_c + st_t [w]x(r, c)
-  R[0] = ct + a_wxv * (w[0] * w[0]);
-  R[1] = a_wxv * (w[1] * w[0]) + st_t * w[2];
-  R[2] = a_wxv * (w[2] * w[0]) - st_t * w[1];
-  R[3] = a_wxv * (w[0] * w[1]) - st_t * w[2];
-  R[4] = ct + a_wxv * (w[1] * w[1]);
-  R[5] = a_wxv * (w[2] * w[1]) + st_t * w[0];
-  R[6] = a_wxv * (w[0] * w[2]) + st_t * w[1];
-  R[7] = a_wxv * (w[1] * w[2]) - st_t * w[0];
-  R[8] = ct + a_wxv * (w[2] * w[2]);
-  const T wv = w[0] * v[0] + w[1] * v[1] + w[2] * v[2];
-  const T wxv[3] = {w[1] * v[2] - w[2] * v[1], w[2] * v[0] - w[0] * v[2], w[0] * v[1] - w[1] * v[0]};
-  for (int e = 0; e < 3; ++e) p[e] = st_t * v[e] + a_w * wv * w[e] + a_wxv * wxv[e];
-}
-
-// pinocchio SpecialEuclideanOperationTpl<3>::integrate: M1 = M0 exp6(dq); the
-// quaternion re-extracted from M1's rotation, flipped into q0's hemisphere and
-// first-order normalised. q7 = (p, quat xyzw); out may not alias q7.
-MB_HD inline void ff_integrate(const double* q7, const double* dq, double* out) {
-  double R0[9], Re[9], pe[3], R1[9], t[3];
-  quat_to_R(q7 + 3, R0);
-  exp6_t<double>(dq, Re, pe);
-  matmul3(R0, Re, R1);
-  matvec3(R0, pe, t);
-  out[0] = q7[0] + t[0];
-  out[1] = q7[1] + t[1];
-  out[2] = q7[2] + t[2];
-  double qn[4];
-  R_to_quat(R1, qn);
-  const double dd = qn[0] * q7[3] + qn[1] * q7[4] + qn[2] * q7[5] + qn[3] * q7[6];
-  const double sg = dd < 0. ? -1. : 1.;
-  const double n2 = qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3];
-  const double al = sg * (3. - n2) * 0.5;
-  for (int e = 0; e < 4; ++e) out[3 + e] = qn[e] * al;
-}
-// pinocchio SpecialEuclideanOperationTpl<3>::difference: log6(M0^-1 M1).
-MB_HD inline void ff_difference(const double* q0, const double* q1, double* out) {
-  double R0[9], R1[9], Rr[9], dp[3], pr[3];
-  quat_to_R(q0 + 3, R0);
-  quat_to_R(q1 + 3, R1);
-  matTmul3(R0, R1, Rr);
-  dp[0] = q1[0] - q0[0];
-  dp[1] = q1[1] - q0[1];
-  dp[2] = q1[2] - q0[2];
-  matTvec3(R0, dp, pr);
-  log6_t<double>(Rr, pr, out);
-}
-// column k of Jexp6(nu) (pinocchio Jexp6, the right Jacobian: exp6(nu + e eps)
-// = exp6(nu) exp6(J e eps)): the twist of exp6(nu)^-1 d exp6(nu + eps e_k).
-MB_HD inline void jexp6_col(const double* nu, int k, double* col) {
-  Dual n[6], R[9], p[3];
-  for (int e = 0; e < 6; ++e) n[e] = Dual{nu[e], e == k ? 1. : 0.};
-  exp6_t<Dual>(n, R, p);
-  double Rv[9], dR[9], dp[3], Om[9];
-  for (int e = 0; e < 9; ++e) {
-    Rv[e] = R[e].v;
-    dR[e] = R[e].d;
-  }
-  for (int e = 0; e < 3; ++e) dp[e] = p[e].d;
-  matTvec3(Rv, dp, col);
-  matTmul3(Rv, dR, Om);  // [xi_ang]x
-  col[3] = Om[5];        // (2,1)
-  col[4] = Om[6];        // (0,2)
-  col[5] = Om[1];        // (1,0)
-}
-// column k of Jlog6(M) (pinocchio Jlog6: log6(M exp6(e eps)) = log6(M) + J e eps)
-MB_HD inline void jlog6_col(const double* R, const double* p, int k, double* col) {
-  double xi[6] = {0., 0., 0., 0., 0., 0.};
-  xi[k] = 1.;
-  double dR[9], dp[3];
-  for (int c = 0; c < 3; ++c) {  // dR = R [xi_ang]x
-    double t[3];
-    const double e[3] = {c == 0 ? 1. : 0., c == 1 ? 1. : 0., c == 2 ? 1. : 0.};
-    cross3(xi + 3, e, t);
-    matvec3(R, t, dR + 3 * c);
-  }
-  matvec3(R, xi, dp);
-  Dual RD[9], PD[3], o[6];
-  for (int e = 0; e < 9; ++e) RD[e] = Dual{R[e], dR[e]};
-  for (int e = 0; e < 3; ++e) PD[e] = Dual{p[e], dp[e]};
-  log6_t<Dual>(RD, PD, o);
-  for (int e = 0; e < 6; ++e) col[e] = o[e].d;
-}
-
-// ---------------------------------------------------------------------------
-// World-frame values. Spatial quantities are expressed at the world origin in
-// world axes, so every recursion of RNEA/CRBA becomes a sum over the ancestors or
-// the subtree of a dof
-//   v_i = sum_{k in anc(i)} S_k qd_k,  a_i = -g + sum_{k in anc(i)} (S_k qdd_k + v_k x S_k qd_k),
-//   tau_i = S_i . sum_{k in sub(i)} f_k,  Ic_i = sum_{k in sub(i)} I_k,
-//   M_ij = S_i . (Ic_j S_j)  (i in anc(j)),
-// which each lane evaluates for its own dof: no serial chain through LDS.
-// anc(i) holds every dof of the ancestor-or-self bodies (all six free-flyer
-// dofs for the base), so v_k is the full body velocity. The placements
-// oMi = oMparent * liMi are composed by each lane walking its ancestors (w_walk).
-// ---------------------------------------------------------------------------
-// The world values of a dof in two records of kWRec doubles (40 used, 2 of padding): the
-// L record holds what outlives the recursions (placement oMi, motion subspace, velocity,
-// acceleration, composite inertia), the D record what the recursions alone use (the local
-// placement, body mass / CoM / inertia, the RNEA's forces and terms). The workgroup's lanes
-// read and write their own dof's records (lane stride kWRec): at a multiple of 32 doubles
-// every lane of a 64-bit access would map to the same bank pair; at 42 (84 dwords) the lanes
-// spread over 16 bank pairs (2-way) with the records 16-byte aligned. (One 80-double record
-// per dof, its round-5 layout, was a 16-way conflict: C5 rollout 28.55 -> 26.81 ms,
-// calcDiff 25.60 -> 25.26 ms when padded.) The D records may lie apart from the L records
-// (`aux`): the rollout's calc puts its factorisation over them once the recursions are done
-// (knot_calc_dense_x); by default they follow the L records, the ancestor masks and root_a.
-constexpr int kWRec = 42;
-constexpr int kMaxCosts = 64;
-struct WVals {
-  double* base;
-  int nj;
-  double* parts;  // per-wave partial sums of the recursions: 4 x 6 per dof (kPartDoubles)
-  double* aux;    // the D records
-  MB_HD WVals(double* b, int n, double* p, double* a = nullptr)
-      : base(b), nj(n), parts(p), aux(a ? a : b + lsize(n)) {}
-  MB_HD double* L(int i) const { return mb_lds(base + kWRec * i); }
-  MB_HD double* Dr(int i) const { return mb_lds(aux + kWRec * i); }
-  MB_HD double* oR(int i) const { return L(i); }  // oMi
-  MB_HD double* op(int i) const { return L(i) + 9; }
-  MB_HD double* S(int i) const { return L(i) + 12; }   // dof motion subspace (world)
-  MB_HD double* v(int i) const { return L(i) + 18; }
-  MB_HD double* a(int i) const { return L(i) + 24; }
-  MB_HD double* cm(int i) const { return L(i) + 30; }  // composite inertia, origin form: m, h = m c, I_O (6)
-  MB_HD double* ch(int i) const { return L(i) + 31; }
-  MB_HD double* cI(int i) const { return L(i) + 34; }
-  MB_HD double* R(int i) const { return Dr(i); }  // liMi rotation
-  MB_HD double* p(int i) const { return Dr(i) + 9; }
-  MB_HD double* m(int i) const { return Dr(i) + 12; }   // body mass (0 on the massless free-flyer dofs)
-  MB_HD double* c(int i) const { return Dr(i) + 13; }   // body CoM (world)
-  MB_HD double* Ic(int i) const { return Dr(i) + 16; }  // body inertia about its CoM, world axes (6)
-  MB_HD double* F(int i) const { return Dr(i) + 22; }   // body force, then accumulated joint force
-  MB_HD double* cq(int i) const { return Dr(i) + 28; }  // S_i qdd_i + v_i x S_i qd_i
-  MB_HD double* fb(int i) const { return Dr(i) + 34; }  // body force I a + v x* I v
-  // per-wave partial sums of the ancestor / subtree recursions (wave w's share of the dofs)
-  MB_HD double* part(int w, int i) const { return mb_lds(parts + 6 * ((int64_t)w * nj + i)); }
-  MB_HD Mask* anc(int i) const { return (Mask*)(base + kWRec * nj) + i; }  // ancestors-or-self dofs
-  MB_HD double* root_a() const { return mb_lds(base + kWRec * nj + nj); }
-  // the L records, the masks and root_a; the D records
-  MB_HD static int64_t lsize(int nj) { return pad2((int64_t)kWRec * nj + nj + 6); }
-  MB_HD static int64_t dsize(int nj) { return (int64_t)kWRec * nj; }
-  MB_HD static int64_t doubles(int nj) { return lsize(nj) + dsize(nj); }
-};
-
-// The per-wave partial sums (RNEA recursions: 6 per dof, composites: 10 per dof) come
-// from at most kPartWaves waves (their LDS areas are sized for that); larger workgroups
-// leave the other waves idle in those phases.
-constexpr int kPartWaves = 4;
-MB_HD __forceinline__ int part_waves(int nt) { return (nt >> 6) < kPartWaves ? (nt >> 6) : kPartWaves; }
-// (6 per dof for the RNEA sums, 10 for the composites)
-MB_HD __forceinline__ int64_t part_doubles(int nj) { return (int64_t)kPartWaves * 10 * nj; }
-
-// lane i < nj: local placement (buffer A starts as liMi), ancestor bits.
-MB_HD inline void w_joint_local(const Blk& b, const WVals& W, const double* q, int i) {
-  double R[9], p[3];
-  if (b.ff && i < 6) {
-    if (i == 0) {  // base pose: root placement * (R(quat), p)
-      const JRec J(b, 0);
-      double Rq[9], t[3];
-      quat_to_R(q + 3, Rq);
-      matmul3(J.Rpl(), Rq, R);
-      matvec3(J.Rpl(), q, t);
-      for (int e = 0; e < 3; ++e) p[e] = J.ppl()[e] + t[e];
-    } else {
-      for (int e = 0; e < 9; ++e) R[e] = (e % 4 == 0) ? 1. : 0.;
-      for (int e = 0; e < 3; ++e) p[e] = 0.;
-    }
-  } else {
-    const JRec J(b, rec_of(b, i));
-    double ax[3], Rpl[9];
-    for (int e = 0; e < 3; ++e) ax[e] = J.axis()[e];
-    for (int e = 0; e < 9; ++e) Rpl[e] = J.Rpl()[e];
-    joint_rotation(Rpl, ax, q[qof(b, i)], R);
-    for (int e = 0; e < 3; ++e) p[e] = J.ppl()[e];
-  }
-  for (int e = 0; e < 9; ++e) {
-    W.R(i)[e] = R[e];
-    W.oR(i)[e] = R[e];
-  }
-  for (int e = 0; e < 3; ++e) {
-    W.p(i)[e] = p[e];
-    W.op(i)[e] = p[e];
-  }
-  if (i == 0) {
-    for (int e = 0; e < 6; ++e) W.root_a()[e] = e < 3 ? -b.g[e] : 0.;
-  }
-  *W.anc(i) = anc_mask(b, i);
-}
-
-// lane i < nj: oMi = L_root ... L_i, the local placements of i's ancestors composed
-// by walking its ancestor mask from i towards the root (parents precede children):
-// one phase, no barrier per level, and the loads do not wait on the products (the
-// pointer-jumping rounds this replaced took ceil(log2 nj) barrier phases). The free-flyer's
-// dofs 1..5 carry identity placements and are skipped (exact).
-MB_HD inline void w_walk(const Blk& b, const WVals& W, int i) {
-  double R[9], p[3];
-  for (int e = 0; e < 9; ++e) R[e] = W.R(i)[e];
-  for (int e = 0; e < 3; ++e) p[e] = W.p(i)[e];
-  Mask m = *W.anc(i) & ~(1ull << i);
-  if (b.ff) m &= ~0x3Eull;
-  while (m) {
-    const int k = 63 - __builtin_clzll(m);
-    m &= ~(1ull << k);
-    double Rk[9], pk[3], Rn[9], t[3];
-    for (int e = 0; e < 9; ++e) Rk[e] = W.R(k)[e];
-    for (int e = 0; e < 3; ++e) pk[e] = W.p(k)[e];
-    matmul3(Rk, R, Rn);
-    matvec3(Rk, p, t);
-    for (int e = 0; e < 9; ++e) R[e] = Rn[e];
-    for (int e = 0; e < 3; ++e) p[e] = pk[e] + t[e];
-  }
-  for (int e = 0; e < 9; ++e) W.oR(i)[e] = R[e];
-  for (int e = 0; e < 3; ++e) W.op(i)[e] = p[e];
-}
-
-// lane i < nj: world motion subspace and body inertia from oMi (oR/op).
-MB_HD inline void w_joint_world(const Blk& b, const WVals& W, int i) {
-  double oR[9], op[3], w[3], ax[3];
-  for (int e = 0; e < 9; ++e) oR[e] = W.oR(i)[e];
-  for (int e = 0; e < 3; ++e) op[e] = W.op(i)[e];
-  dof_axis(b, i, ax);
-  matvec3(oR, ax, w);
-  if (dof_prismatic(b, i)) {
-    for (int e = 0; e < 3; ++e) {
-      W.S(i)[e] = w[e];
-      W.S(i)[3 + e] = 0.;
-    }
-  } else {
-    double vl[3];
-    cross3(op, w, vl);  // velocity of the world origin: w x (0 - op) = op x w
-    for (int e = 0; e < 3; ++e) {
-      W.S(i)[e] = vl[e];
-      W.S(i)[3 + e] = w[e];
-    }
-  }
-  double* o = W.Ic(i);
-  if (!carries_body(b, i)) {
-    *W.m(i) = 0.;
-    for (int e = 0; e < 3; ++e) W.c(i)[e] = op[e];
-    for (int e = 0; e < 6; ++e) o[e] = 0.;
-    return;
-  }
-  const JRec J(b, rec_of(b, i));
-  double c[3], t[3];
-  matvec3(oR, J.com(), t);
-  for (int e = 0; e < 3; ++e) c[e] = op[e] + t[e];
-  // Ic_w = oR Ic oR^T
-  const double* s = J.I6();
-  const double Is[9] = {s[0], s[3], s[4], s[3], s[1], s[5], s[4], s[5], s[2]};
-  double tmp[9], Iw[9];
-  matmul3(oR, Is, tmp);
-  for (int r = 0; r < 3; ++r)
-    for (int cc = 0; cc < 3; ++cc) Iw[cc * 3 + r] = tmp[r] * oR[cc] + tmp[3 + r] * oR[3 + cc] + tmp[6 + r] * oR[6 + cc];
-  for (int e = 0; e < 3; ++e) W.c(i)[e] = c[e];
-  *W.m(i) = J.mass();
-  o[0] = Iw[0];
-  o[1] = Iw[4];
-  o[2] = Iw[8];
-  o[3] = Iw[3];
-  o[4] = Iw[6];
-  o[5] = Iw[7];
-}
-
-// wave w's contiguous share [w c, (w + 1) c), c = ceil(nj / nw), of nj dofs
-MB_HD __forceinline__ void k_range(int nj, int w, int nw, int& k0, int& k1) {
-  const int c = (nj + nw - 1) / nw;
-  k0 = w * c;
-  k1 = k0 + c < nj ? k0 + c : nj;
-}
-// Per-record work on one lane each, from the top of the workgroup down: record k on
-// lane nt - 1 - 64 (k mod W) - k / W (W waves), i.e. one record per wave before any wave
-// takes a second (a wave runs its divergent lanes' paths one after another).
-MB_HD __forceinline__ int spread_lane(int k, int nt) {
-  const int nwv = nt >> 6;
-  return nt - 1 - 64 * (k % nwv) - k / nwv;
-}
-MB_HD __forceinline__ int spread_item(int lane, int nt) {
-  const int u = nt - 1 - lane, nwv = nt >> 6;
-  return (u & 63) * nwv + (u >> 6);
-}
-// composite inertia of dof i's subtree times a motion x: (m v - h x w, I_O w + h x v)
-MB_HD __forceinline__ void comp_mul(const WVals& W, int i, const double* x, double* o) {
-  const double m = *W.cm(i);
-  const double* h = W.ch(i);
-  const double* I = W.cI(i);
-  double t[3];
-  cross3(h, x + 3, t);
-  for (int e = 0; e < 3; ++e) o[e] = m * x[e] - t[e];
-  cross3(h, x, t);
-  o[3] = I[0] * x[3] + I[3] * x[4] + I[4] * x[5] + t[0];
-  o[4] = I[3] * x[3] + I[1] * x[4] + I[5] * x[5] + t[1];
-  o[5] = I[4] * x[3] + I[5] * x[4] + I[2] * x[5] + t[2];
-}
-
-// lane i < nj: v_i = sum over ancestors-or-self of S_k qd_k
-MB_HD inline void w_velocity(const WVals& W, const double* qd, int i) {
-  double v[6] = {0., 0., 0., 0., 0., 0.};
-  const Mask am = *W.anc(i);
-  // every dof's terms loaded, the others' selected away (not branched around), so the
-  // unrolled iterations' LDS loads overlap; the sums keep their order
-#pragma unroll 2
-  for (int k = 0; k < W.nj; ++k) {
-    const bool in = (am >> k) & 1ull;
-    const double w = qd[k];
-    for (int e = 0; e < 6; ++e) {
-      const double t = W.S(k)[e] * w;
-      v[e] += in ? t : 0.;
-    }
-  }
-  for (int e = 0; e < 6; ++e) W.v(i)[e] = v[e];
-}
-
-// lane i < nj: cq_i = S_i qdd_i + v_i x (S_i qd_i)
-MB_HD inline void w_accel_term(const WVals& W, const double* qd, const double* qdd, int i) {
-  double S[6], v[6], Sw[6], t6[6];
-  const double w = qd[i], qa = qdd ? qdd[i] : 0.;
-  for (int e = 0; e < 6; ++e) {
-    S[e] = W.S(i)[e];
-    v[e] = W.v(i)[e];
-    Sw[e] = S[e] * w;
-  }
-  cross_m(v, Sw, t6);
-  for (int e = 0; e < 6; ++e) W.cq(i)[e] = S[e] * qa + t6[e];
-}
-
-// lane i < nj: a_i = -g + sum over ancestors-or-self of cq_k, then the body
-// force f_i = I_i a_i + v_i x* (I_i v_i) - fext_i
-MB_HD inline void w_accel_force(const WVals& W, int i, const double* fx = nullptr) {
-  double a[6];
-  for (int e = 0; e < 6; ++e) a[e] = W.root_a()[e];
-  const Mask am = *W.anc(i);
-#pragma unroll 2
-  for (int k = 0; k < W.nj; ++k) {  // (selected, not branched: as w_velocity)
-    const bool in = (am >> k) & 1ull;
-    for (int e = 0; e < 6; ++e) {
-      const double t = W.cq(k)[e];
-      a[e] += in ? t : 0.;
-    }
-  }
-  double v[6], f[6], Iv[6], t6[6], c[3], I6[6];
-  for (int e = 0; e < 6; ++e) {
-    W.a(i)[e] = a[e];
-    v[e] = W.v(i)[e];
-    I6[e] = W.Ic(i)[e];
-  }
-  for (int e = 0; e < 3; ++e) c[e] = W.c(i)[e];
-  const double m = *W.m(i);
-  inertia_mul(m, c, I6, a, f);
-  inertia_mul(m, c, I6, v, Iv);
-  cross_f(v, Iv, t6);
-  for (int e = 0; e < 6; ++e) W.fb(i)[e] = f[e] + t6[e] - (fx ? fx[6 * i + e] : 0.);
-}
-
-// lane i < nj: F_i = sum over the subtree of the body forces, tau_i = S_i . F_i
-MB_HD inline void w_joint_force(const Blk& b, const WVals& W, double* tau, int i) {
-  double F[6] = {0., 0., 0., 0., 0., 0.};
-#pragma unroll 2
-  for (int k = 0; k < b.nj; ++k) {  // (selected, not branched: as w_velocity)
-    const bool in = (*W.anc(k) >> i) & 1ull;
-    for (int e = 0; e < 6; ++e) {
-      const double t = W.fb(k)[e];
-      F[e] += in ? t : 0.;
-    }
-  }
-  for (int e = 0; e < 6; ++e) W.F(i)[e] = F[e];
-  tau[i] = dot6(W.S(i), F);
-}
-
-// lane j < nj of wave w (of nw): CRBA column j in world frame, F = Ic_j S_j, M_ij = S_i . F
-// for the ancestors-or-self i < j of j (+ armature on the diagonal), the rows i < j split
-// in nw contiguous ranges, one per wave (the waves run side by side: the per-lane chain
-// of LDS loads is a quarter as long). A: ld lda, zeroed.
-// The column is formed about the point P = joint j's origin, not the world origin: the
-// subtree's composite inertia is summed from the bodies' offsets c_b - P, and the motion
-// subspaces are shifted to P (S_i at P: [w_i x (P - p_i); w_i], a prismatic dof [w_i; 0]).
-// About the world origin the entries of a light distal link (a gripper, 1e-4 kg m^2, 1 m
-// from the origin) are the difference of terms ~ m |c|^2 ~ 0.3, which cost ~3 digits of
-// M and, through cond(M) ~ 1e6, of M^-1 and Fu (the round-4 parity trace); at P the
-// lever arms are the link's own size.
-// Phase 1 (lane j of wave w < nw): wave w's share of j's subtree bodies into its
-// partial (W.parts, 10 per dof: m, h, I about P_j), as w_composite.
-MB_HD inline void w_crba_composite_part(const Blk& b, const WVals& W, int j, int w, int nw) {
-  double P[3], m = 0., h[3] = {0., 0., 0.}, I[6] = {0., 0., 0., 0., 0., 0.};
-  for (int e = 0; e < 3; ++e) P[e] = W.op(j)[e];
-  int k0 = b.ff ? 5 : 0, k1 = b.nj;
-  if (nw > 1) k_range(b.nj, w, nw, k0, k1);
-  if (b.ff && k0 < 5) k0 = 5;
-  // (every body of the share read, the others weighted 0: the loads overlap)
-#pragma unroll 2
-  for (int k = k0; k < k1; ++k) {
-    const double sel = ((*W.anc(k) >> j) & 1ull) ? 1. : 0.;
-    const double mk = *W.m(k);
-    double c[3], Ic[6];
-    for (int e = 0; e < 3; ++e) c[e] = W.c(k)[e] - P[e];
-    for (int e = 0; e < 6; ++e) Ic[e] = W.Ic(k)[e];
-    const double cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
-    m += sel * mk;
-    for (int e = 0; e < 3; ++e) h[e] += sel * (mk * c[e]);
-    I[0] += sel * (Ic[0] + mk * (cc - c[0] * c[0]));
-    I[1] += sel * (Ic[1] + mk * (cc - c[1] * c[1]));
-    I[2] += sel * (Ic[2] + mk * (cc - c[2] * c[2]));
-    I[3] += sel * (Ic[3] - mk * c[0] * c[1]);
-    I[4] += sel * (Ic[4] - mk * c[0] * c[2]);
-    I[5] += sel * (Ic[5] - mk * c[1] * c[2]);
-  }
-  double* o = mb_lds(W.parts + 10 * ((int64_t)w * b.nj + j));
-  o[0] = m;
-  for (int e = 0; e < 3; ++e) o[1 + e] = h[e];
-  for (int e = 0; e < 6; ++e) o[4 + e] = I[e];
-}
-// Phase 2 (lane j of wave w of nw): the partials of the npw waves combined in wave order,
-// F = Ic_j S_j about P_j, M_ij = S_i(P_j) . F for the ancestors-or-self i < j of j (+
-// armature on the diagonal), the rows i < j split in nw contiguous ranges, one per wave.
-// A: ld lda, zeroed.
-// store_world: wave 0 also stores the subtree composite about the world origin (W.cm /
-// ch / cI, the calcDiff's recursions): h_O = h + m P, I_O = I + 2 (h.P) 1 - (h P^T +
-// P h^T) + m (|P|^2 1 - P P^T) (the same terms as summing the bodies about the origin).
-// (the partials of the npw waves combined in wave order)
-MB_HD __forceinline__ void w_crba_combine(const WVals& W, int nj, int j, int npw, double* v) {
-  const double* p0 = mb_lds(W.parts + 10 * (int64_t)j);
-  for (int e = 0; e < 10; ++e) v[e] = p0[e];
-  for (int ww = 1; ww < npw; ++ww) {
-    const double* p = mb_lds(W.parts + 10 * ((int64_t)ww * nj + j));
-    for (int e = 0; e < 10; ++e) v[e] += p[e];
-  }
-}
-// combined: the composite about P_j already in W.cm / ch / cI (w_crba_store_local; the
-// partials may be overwritten meanwhile)
-MB_HD inline void w_crba_column(const Blk& b, const WVals& W, int j, double* A, int lda, int w, int nw, int npw,
-                                bool store_world = false, bool combined = false) {
-  double P[3], v[10];
-  for (int e = 0; e < 3; ++e) P[e] = W.op(j)[e];
-  if (combined) {
-    v[0] = *W.cm(j);
-    for (int e = 0; e < 3; ++e) v[1 + e] = W.ch(j)[e];
-    for (int e = 0; e < 6; ++e) v[4 + e] = W.cI(j)[e];
-  } else {
-    w_crba_combine(W, b.nj, j, npw, v);
-  }
-  const double m = v[0];
-  const double* h = v + 1;
-  const double* I = v + 4;
-  if (store_world && w == 0) {
-    const double hp = h[0] * P[0] + h[1] * P[1] + h[2] * P[2], pp = P[0] * P[0] + P[1] * P[1] + P[2] * P[2];
-    *W.cm(j) = m;
-    for (int e = 0; e < 3; ++e) W.ch(j)[e] = h[e] + m * P[e];
-    // (I ordering: xx, yy, zz, xy, xz, yz)
-    W.cI(j)[0] = I[0] + 2. * (hp - h[0] * P[0]) + m * (pp - P[0] * P[0]);
-    W.cI(j)[1] = I[1] + 2. * (hp - h[1] * P[1]) + m * (pp - P[1] * P[1]);
-    W.cI(j)[2] = I[2] + 2. * (hp - h[2] * P[2]) + m * (pp - P[2] * P[2]);
-    W.cI(j)[3] = I[3] - (h[0] * P[1] + P[0] * h[1]) - m * P[0] * P[1];
-    W.cI(j)[4] = I[4] - (h[0] * P[2] + P[0] * h[2]) - m * P[0] * P[2];
-    W.cI(j)[5] = I[5] - (h[1] * P[2] + P[1] * h[2]) - m * P[1] * P[2];
-  }
-  // S_i shifted to P: [S_i.lin + S_i.ang x P; S_i.ang] (a revolute dof's axis w through
-  // p_i moves P at w x (P - p_i) = S_i.lin + w x P; a prismatic dof has S_i.ang = 0).
-  // The products are dimension-one in the lever arms, so forming them from the world-origin
-  // S_i costs only the rounding of the placements (unlike the quadratic m |c|^2 terms).
-  // Scalars throughout: a shifted-S array written under a branch lands in scratch memory.
-  const double* Sjw = W.S(j);
-  const double sj3 = Sjw[3], sj4 = Sjw[4], sj5 = Sjw[5];
-  const double sj0 = Sjw[0] + (sj4 * P[2] - sj5 * P[1]);
-  const double sj1 = Sjw[1] + (sj5 * P[0] - sj3 * P[2]);
-  const double sj2 = Sjw[2] + (sj3 * P[1] - sj4 * P[0]);
-  // F = Ic_j S_j about P: (m v - h x w, I w + h x v)
-  const double F0 = m * sj0 - (h[1] * sj5 - h[2] * sj4);
-  const double F1 = m * sj1 - (h[2] * sj3 - h[0] * sj5);
-  const double F2 = m * sj2 - (h[0] * sj4 - h[1] * sj3);
-  const double F3 = I[0] * sj3 + I[3] * sj4 + I[4] * sj5 + (h[1] * sj2 - h[2] * sj1);
-  const double F4 = I[3] * sj3 + I[1] * sj4 + I[5] * sj5 + (h[2] * sj0 - h[0] * sj2);
-  const double F5 = I[4] * sj3 + I[5] * sj4 + I[2] * sj5 + (h[0] * sj1 - h[1] * sj0);
-  if (w == 0) A[(int64_t)j * lda + j] = (sj0 * F0 + sj1 * F1 + sj2 * F2) + (sj3 * F3 + sj4 * F4 + sj5 * F5) + b.arm[j];
-  const Mask am = *W.anc(j);
-  const int ch = (j + nw - 1) / nw, i0 = w * ch, i1 = i0 + ch < j ? i0 + ch : j;
-  // every i < j visited, the non-ancestors storing their zero (only lane j writes the
-  // pair {i, j}), so the loop has no branch and the unrolled loads overlap
-#pragma unroll 2
-  for (int i = i0; i < i1; ++i) {
-    const double* Si = W.S(i);
-    const double a3 = Si[3], a4 = Si[4], a5 = Si[5];
-    const double l0 = Si[0] + (a4 * P[2] - a5 * P[1]);
-    const double l1 = Si[1] + (a5 * P[0] - a3 * P[2]);
-    const double l2 = Si[2] + (a3 * P[1] - a4 * P[0]);
-    const double d = (l0 * F0 + l1 * F1 + l2 * F2) + (a3 * F3 + a4 * F4 + a5 * F5);
-    const double Mij = ((am >> i) & 1ull) ? d : 0.;
-    A[(int64_t)j * lda + i] = Mij;
-    A[(int64_t)i * lda + j] = Mij;
-  }
-}
-
-// lane j: the subtree composite about P_j (the combined partials) into W.cm / ch / cI, so
-// that the columns can overwrite the partials (the rollout's calc, knot_calc_dense_x)
-MB_HD inline void w_crba_store_local(const WVals& W, int nj, int j, int npw) {
-  double v[10];
-  w_crba_combine(W, nj, j, npw, v);
-  *W.cm(j) = v[0];
-  for (int e = 0; e < 3; ++e) W.ch(j)[e] = v[1 + e];
-  for (int e = 0; e < 6; ++e) W.cI(j)[e] = v[4 + e];
-}
-
-// ---- the RNEA recursions split over the waves ---------------------------------
-// Each ancestor (or subtree) sum of lane i runs over the dofs k in wave w's contiguous
-// range [w c, (w + 1) c), c = ceil(nj / nw), into part(w, i); the next phase combines
-// the nw partials in wave order. (The sums' association changes, not their terms.)
-MB_HD __forceinline__ void combine6(const WVals& W, int i, int nw, double* o) {
-  for (int e = 0; e < 6; ++e) o[e] = W.part(0, i)[e];
-  for (int w = 1; w < nw; ++w)
-    for (int e = 0; e < 6; ++e) o[e] += W.part(w, i)[e];
-}
-// lane i, wave w: sum over ancestors-or-self k in w's range of S_k qd_k
-MB_HD inline void w_velocity_part(const WVals& W, const double* qd, int i, int w, int nw) {
-  double v[6] = {0., 0., 0., 0., 0., 0.};
-  const Mask am = *W.anc(i);
-  int k0, k1;
-  k_range(W.nj, w, nw, k0, k1);
-#pragma unroll 2
-  for (int k = k0; k < k1; ++k) {
-    const bool in = (am >> k) & 1ull;
-    const double qk = qd[k];
-    for (int e = 0; e < 6; ++e) {
-      const double t = W.S(k)[e] * qk;
-      v[e] += in ? t : 0.;
-    }
-  }
-  for (int e = 0; e < 6; ++e) W.part(w, i)[e] = v[e];
-}
-// lane i, wave w: sum over ancestors-or-self k in w's range of cq_k
-MB_HD inline void w_accel_part(const WVals& W, int i, int w, int nw) {
-  double a[6] = {0., 0., 0., 0., 0., 0.};
-  const Mask am = *W.anc(i);
-  int k0, k1;
-  k_range(W.nj, w, nw, k0, k1);
-#pragma unroll 2
-  for (int k = k0; k < k1; ++k) {
-    const bool in = (am >> k) & 1ull;
-    for (int e = 0; e < 6; ++e) {
-      const double t = W.cq(k)[e];
-      a[e] += in ? t : 0.;
-    }
-  }
-  for (int e = 0; e < 6; ++e) W.part(w, i)[e] = a[e];
-}
-// lane i, wave w: sum over the subtree bodies k in w's range of the body forces
-MB_HD inline void w_force_part(const WVals& W, int i, int w, int nw) {
-  double F[6] = {0., 0., 0., 0., 0., 0.};
-  int k0, k1;
-  k_range(W.nj, w, nw, k0, k1);
-#pragma unroll 2
-  for (int k = k0; k < k1; ++k) {
-    const bool in = (*W.anc(k) >> i) & 1ull;
-    for (int e = 0; e < 6; ++e) {
-      const double t = W.fb(k)[e];
-      F[e] += in ? t : 0.;
-    }
-  }
-  for (int e = 0; e < 6; ++e) W.part(w, i)[e] = F[e];
-}
-// lane i: v_i from the partials, then cq_i = S_i qdd_i + v_i x (S_i qd_i)
-MB_HD inline void w_velocity_accel_term(const WVals& W, const double* qd, const double* qdd, int i, int nw) {
-  double v[6];
-  combine6(W, i, nw, v);
-  for (int e = 0; e < 6; ++e) W.v(i)[e] = v[e];
-  double S[6], Sw[6], t6[6];
-  const double wq = qd[i], qa = qdd ? qdd[i] : 0.;
-  for (int e = 0; e < 6; ++e) {
-    S[e] = W.S(i)[e];
-    Sw[e] = S[e] * wq;
-  }
-  cross_m(v, Sw, t6);
-  for (int e = 0; e < 6; ++e) W.cq(i)[e] = S[e] * qa + t6[e];
-}
-// lane i: a_i = -g + the partials, then the body force f_i = I_i a_i + v_i x* (I_i v_i) - fext_i
-MB_HD inline void w_accel_body_force(const WVals& W, int i, int nw, const double* fx) {
-  double a[6], p[6];
-  combine6(W, i, nw, p);
-  for (int e = 0; e < 6; ++e) a[e] = W.root_a()[e] + p[e];
-  double v[6], f[6], Iv[6], t6[6], c[3], I6[6];
-  for (int e = 0; e < 6; ++e) {
-    W.a(i)[e] = a[e];
-    v[e] = W.v(i)[e];
-    I6[e] = W.Ic(i)[e];
-  }
-  for (int e = 0; e < 3; ++e) c[e] = W.c(i)[e];
-  const double m = *W.m(i);
-  inertia_mul(m, c, I6, a, f);
-  inertia_mul(m, c, I6, v, Iv);
-  cross_f(v, Iv, t6);
-  for (int e = 0; e < 6; ++e) W.fb(i)[e] = f[e] + t6[e] - (fx ? fx[6 * i + e] : 0.);
-}
-// lane i: F_i from the partials, tau_i = S_i . F_i
-MB_HD inline void w_joint_force_comb(const WVals& W, double* tau, int i, int nw) {
-  double F[6];
-  combine6(W, i, nw, F);
-  for (int e = 0; e < 6; ++e) W.F(i)[e] = F[e];
-  tau[i] = dot6(W.S(i), F);
-}
-
-// Cost records
-struct CRec {
-  const double* r;
-  MB_HD int type() const { return (int)mb_lds(r)[0]; }
-  MB_HD double weight() const { return mb_lds(r)[1]; }
-  MB_HD int size() const { return (int)mb_lds(r)[3]; }
-  MB_HD const double* d() const { return mb_lds(r + kCHdr); }
-};
-
-// dof carrying the frame of a frame / contact payload d = [joint record, R 9, p 3, ...]
-MB_HD __forceinline__ int frame_dof(const Blk& b, const double* d) { return dof_of_rec(b, (int)d[0]); }
-
-// oMf of a frame payload
-MB_HD inline void frame_placement(const Blk& b, const WVals& V, const double* d, double* R, double* p) {
-  const int j = frame_dof(b, d);
-  matmul3(V.oR(j), d + 1, R);
-  matvec3(V.oR(j), d + 10, p);
-  p[0] += V.op(j)[0];
-  p[1] += V.op(j)[1];
-  p[2] += V.op(j)[2];
-}
-
-// Residual of a frame cost and, with S != null (the world motion of a dof that
-// moves the frame), its Jacobian column. Returns the residual size (6 placement,
-// 3 translation).
-MB_HD inline int frame_residual(const Blk& b, const WVals& V, const CRec& C, const double* S, double* r, double* Jc) {
-  const double* d = C.d();
-  double Rf[9], pf[3];
-  frame_placement(b, V, d, Rf, pf);
-  double dR[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.}, dp[3] = {0., 0., 0.};
-  if (S) {  // motion of oMf under S: dp = S_lin + S_ang x pf, dR = [S_ang]x Rf
-    double t[3];
-    cross3(S + 3, pf, t);
-    for (int e = 0; e < 3; ++e) dp[e] = S[e] + t[e];
-    for (int c = 0; c < 3; ++c) cross3(S + 3, Rf + 3 * c, dR + 3 * c);
-  }
-  if (C.type() == C_FRAME_TRANSLATION || C.type() == C_CONTACT_3D) {
-    const double* pref = d + 13;
-    for (int e = 0; e < 3; ++e) {
-      r[e] = pf[e] - pref[e];
-      if (Jc) Jc[e] = dp[e];
-    }
-    for (int e = 3; e < 6; ++e) {
-      r[e] = 0.;
-      if (Jc) Jc[e] = 0.;
-    }
-    return 3;
-  }
-  // rMf = Mref^-1 oMf
-  const double* Rri = d + 13;
-  const double* pri = d + 22;
-  double Rr[9], pr[3], dRr[9], dpr[3];
-  matmul3(Rri, Rf, Rr);
-  matvec3(Rri, pf, pr);
-  pr[0] += pri[0];
-  pr[1] += pri[1];
-  pr[2] += pri[2];
-  matmul3(Rri, dR, dRr);
-  matvec3(Rri, dp, dpr);
-  Dual RD[9], PD[3], o[6];
-  for (int e = 0; e < 9; ++e) RD[e] = Dual{Rr[e], dRr[e]};
-  for (int e = 0; e < 3; ++e) PD[e] = Dual{pr[e], dpr[e]};
-  log6_t<Dual>(RD, PD, o);
-  for (int e = 0; e < 6; ++e) {
-    r[e] = o[e].v;
-    if (Jc) Jc[e] = S ? o[e].d : 0.;
-  }
-  return 6;
-}
-
-// Residual size of a cost record.
-MB_HD inline int cost_nr(const Blk& b, const CRec& C, int nu) {
-  const int t = C.type();
-  if (t == C_CONTACT_FORCE) return (int)C.d()[1];
-  if (t == C_FRICTION_CONE) return (int)C.d()[2];
-  if (t == C_STATE) return 2 * b.nj;
-  if (t == C_CONTROL) return nu;
-  return (t == C_FRAME_PLACEMENT || t == C_FRAME_VELOCITY) ? 6 : 3;
-}
-// The activation of a cost record (its parameters end the record):
-//   Quad / WeightedQuad (quadratic.hpp, weighted-quadratic.hpp:42-71): w (ones if
-//     unweighted); a = 0.5 w r^2, Ar = w r, Arr = w
-//   QuadraticBarrier (quadratic-barrier.hpp:88-117): lb, ub; with rl = min(r - lb, 0),
-//     ru = max(r - ub, 0): a = 0.5 (rl^2 + ru^2), Ar = rl + ru, Arr = [r <= lb or r >= ub]
-//   WeightedQuadraticBarrier (weighted-quadratic-barrier.hpp:35-70): lb, ub, w;
-//     a = 0.5 w^2 (rl^2 + ru^2), Ar = w^2 (rl + ru), Arr = w [r <= lb or r >= ub]
-// Per residual row i: value2 (twice its share of a: callers sum the rows, then
-// halve), sgrad (X * Ar_i, as (X w) r for the quadratic kinds), hess (Arr_ii).
-struct Act {
-  int kind, nr;
-  const double* p;
-  MB_HD __forceinline__ double value2(int i, double r) const {
-    const double* p = mb_lds(this->p);
-    if (kind <= A_WEIGHTED_QUAD) return p[i] * r * r;
-    const double rl = fmin(r - p[i], 0.), ru = fmax(r - p[nr + i], 0.);
-    const double v = rl * rl + ru * ru;
-    return kind == A_WEIGHTED_QUAD_BARRIER ? p[2 * nr + i] * p[2 * nr + i] * v : v;
-  }
-  MB_HD __forceinline__ double sgrad(int i, double r, double X) const {
-    const double* p = mb_lds(this->p);
-    if (kind <= A_WEIGHTED_QUAD) return X * p[i] * r;
-    const double g = fmin(r - p[i], 0.) + fmax(r - p[nr + i], 0.);
-    return X * (kind == A_WEIGHTED_QUAD_BARRIER ? p[2 * nr + i] * p[2 * nr + i] * g : g);
-  }
-  MB_HD __forceinline__ double hess(int i, double r) const {
-    const double* p = mb_lds(this->p);
-    if (kind <= A_WEIGHTED_QUAD) return p[i];
-    const double h = (r - p[i] <= 0.) ? 1. : ((r - p[nr + i] >= 0.) ? 1. : 0.);
-    return kind == A_WEIGHTED_QUAD_BARRIER ? p[2 * nr + i] * h : h;
-  }
-};
-MB_HD inline Act cost_act(const Blk& b, const CRec& C, int nu) {
-  const int nr = cost_nr(b, C, nu), kind = (int)C.r[2];
-  const int np = kind <= A_WEIGHTED_QUAD ? nr : (kind == A_QUAD_BARRIER ? 2 * nr : 3 * nr);
-  return Act{kind, nr, C.r + C.size() - np};
-}
-// costs whose residual Jacobian is dense over the configuration tangent (stored
-// per cost: rows x jw, jw = nj, or 2 nj when a frame-velocity cost needs the
-// velocity columns too): frame costs, CoM, frame velocity, and the free-flyer
-// block of a state cost
-MB_HD __forceinline__ bool jac_cost(const Blk& b, int type) {
-  return type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_COM_POSITION ||
-         type == C_FRAME_VELOCITY || (type == C_STATE && b.ff);
-}
-MB_HD __forceinline__ int jac_rows(int type) {
-  return (type == C_FRAME_TRANSLATION || type == C_COM_POSITION) ? 3 : 6;
-}
-MB_HD inline int count_jac_costs(const Blk& b, bool* vel_cols = nullptr) {
-  int n = 0;
-  bool fv = false;
-  const double* cr = b.C;
-  for (int k = 0; k < b.ncost; ++k) {
-    const CRec C{cr};
-    if (jac_cost(b, C.type())) ++n;
-    if (C.type() == C_FRAME_VELOCITY) fv = true;
-    cr += C.size();
-  }
-  if (vel_cols) *vel_cols = fv;
-  return n;
-}
-// costs on the contact multipliers: CostModelContactForce, CostModelContactFrictionCone
-MB_HD __forceinline__ bool force_cost(int type) { return type == C_CONTACT_FORCE || type == C_FRICTION_CONE; }
-// Residual rows with a dense Jacobian (jac costs; force costs on an active contact
-// when the force Jacobians are computed): the rows of the stacked R of calcDiff.
-MB_HD inline int count_cost_rows(const Blk& b, int nu) {
-  int n = 0;
-  const bool fd = b.enable_force && b.nc > 0 && !b.impulse;
-  const double* cr = b.C;
-  for (int k = 0; k < b.ncost; ++k) {
-    const CRec C{cr};
-    if (jac_cost(b, C.type())) n += jac_rows(C.type());
-    if (fd && force_cost(C.type()) && (int)C.d()[0] >= 0) n += cost_nr(b, C, nu);
-    cr += C.size();
-  }
-  return n;
-}
-// row i of a force cost's residual from the multipliers lam of the contact rows
-// [row0, row0 + nc) (lam unread for an inactive contact: lambda = 0):
-//   contact force: lambda_i - fref_i (contact-force.hxx:33-50: jMf.actInv(f) is the multiplier);
-//   friction cone: A_i . lambda_lin (contact-friction-cone.hxx:58)
-// (lam(k): multiplier k, so that the calc reads it where it lies, sign applied at the use)
-template <class L>
-MB_HD __forceinline__ double force_res_at(const CRec& C, L lam, int i) {
-  const double* d = C.d();
-  const int row0 = (int)d[0];
-  if (C.type() == C_CONTACT_FORCE) return (row0 >= 0 ? lam(row0 + i) : 0.) - d[2 + i];
-  if (row0 < 0) return 0.;
-  const double* A = d + 3 + 3 * i;
-  return A[0] * lam(row0) + A[1] * lam(row0 + 1) + A[2] * lam(row0 + 2);
-}
-MB_HD __forceinline__ double force_res(const CRec& C, const double* lam, int i) {
-  return force_res_at(C, [lam](int k) { return lam[k]; }, i);
-}
-// row i of a force cost's Jacobian column from the multiplier Jacobian column
-// dl[row * ld] (the same linear map as force_res, without the offset)
-MB_HD __forceinline__ double force_jac(const CRec& C, const double* dl, int64_t ld, int i) {
-  const double* d = C.d();
-  const int row0 = (int)d[0];
-  if (C.type() == C_CONTACT_FORCE) return dl[(int64_t)(row0 + i) * ld];
-  const double* A = d + 3 + 3 * i;
-  return A[0] * dl[(int64_t)row0 * ld] + A[1] * dl[(int64_t)(row0 + 1) * ld] + A[2] * dl[(int64_t)(row0 + 2) * ld];
-}
-// activation value of a force cost (inactive contact: lambda = 0)
-template <class L>
-MB_HD __forceinline__ double force_cost_activation_at(const Blk& b, const CRec& C, L lam, int nu) {
-  const Act act = cost_act(b, C, nu);
-  double a = 0.;
-  for (int e = 0; e < act.nr; ++e) a += act.value2(e, force_res_at(C, lam, e));
-  return 0.5 * a;
-}
-MB_HD inline double force_cost_activation(const Blk& b, const CRec& C, const double* lam, int nu) {
-  return force_cost_activation_at(b, C, [lam](int k) { return lam[k]; }, nu);
-}
-
-// Residual of a frame cost, value only (calc). Returns the residual size.
-MB_HD __forceinline__ int frame_residual_value(const Blk& b, const WVals& V, const CRec& C, double* r) {
-  const double* d = C.d();
-  double Rf[9], pf[3];
-  frame_placement(b, V, d, Rf, pf);
-  if (C.type() == C_FRAME_TRANSLATION || C.type() == C_CONTACT_3D) {
-    for (int e = 0; e < 3; ++e) r[e] = pf[e] - d[13 + e];
-    return 3;
-  }
-  double Rr[9], pr[3];
-  matmul3(d + 13, Rf, Rr);
-  matvec3(d + 13, pf, pr);
-  for (int e = 0; e < 3; ++e) pr[e] += d[22 + e];
-  log6_t<double>(Rr, pr, r);
-  return 6;
-}
-
-// Centre of mass (pinocchio::centerOfMass) from the world body CoMs
-MB_HD inline void com_value(const Blk& b, const WVals& W, double* c) {
-  double m = 0., h[3] = {0., 0., 0.};
-  for (int k = 0; k < b.nj; ++k) {
-    if (!carries_body(b, k)) continue;
-    const double mk = *W.m(k);
-    m += mk;
-    for (int e = 0; e < 3; ++e) h[e] += mk * W.c(k)[e];
-  }
-  for (int e = 0; e < 3; ++e) c[e] = h[e] / m;
-}
-
-// free-flyer block of a state residual: log6(Mref^-1 M) (multibody.hxx:69)
-MB_HD inline void ff_rel(const double* xref, const double* x, double* Rr, double* pr) {
-  double R0[9], R1[9], dp[3];
-  quat_to_R(xref + 3, R0);
-  quat_to_R(x + 3, R1);
-  matTmul3(R0, R1, Rr);
-  for (int e = 0; e < 3; ++e) dp[e] = x[e] - xref[e];
-  matTvec3(R0, dp, pr);
-}
-
-// entry i of the state residual diff(xref, x) beyond the free-flyer block
-MB_HD __forceinline__ double state_res(const Blk& b, const double* xref, const double* x, int i) {
-  if (i < b.nj) return x[qof(b, i)] - xref[qof(b, i)];
-  return x[b.nq + i - b.nj] - xref[b.nq + i - b.nj];
-}
-
-// LOCAL velocity of a frame payload d minus vref (pinocchio::getFrameVelocity,
-// frame-velocity.hxx:57-59), from the world body velocities in V.
-MB_HD inline void frame_velocity_res(const Blk& b, const WVals& V, const double* d, double* r) {
-  const int j = frame_dof(b, d);
-  double Rf[9], pf[3], m6[6];
-  frame_placement(b, V, d, Rf, pf);
-  for (int e = 0; e < 6; ++e) m6[e] = V.v(j)[e];
-  motion_act_inv(Rf, pf, m6, r);
-  for (int e = 0; e < 6; ++e) r[e] -= d[13 + e];
-}
-
-// Activation value of one cost record (kinematics in V; velocities in V only with
-// vel: frame-velocity costs are skipped without). Force costs return 0: they need
-// the multipliers and are added after the contact solve.
-MB_HD __forceinline__ double cost_activation(const Blk& b, const WVals& V, const CRec& C, const double* x,
-                                             const double* u, int nu, bool vel = true) {
-  const Act act = cost_act(b, C, nu);
-  double a = 0.;
-  if (C.type() == C_STATE) {
-    const int ndx = 2 * b.nj;
-    int i0 = 0;
-    if (b.ff) {
-      double Rr[9], pr[3], r[6];
-      ff_rel(C.d(), x, Rr, pr);
-      log6_t<double>(Rr, pr, r);
-      for (int e = 0; e < 6; ++e) a += act.value2(e, r[e]);
-      i0 = 6;
-    }
-    for (int i = i0; i < ndx; ++i) a += act.value2(i, state_res(b, C.d(), x, i));
-  } else if (C.type() == C_CONTROL) {
-    for (int i = 0; i < nu; ++i) a += act.value2(i, u[i] - C.d()[i]);
-  } else if (force_cost(C.type())) {
-    return 0.;
-  } else if (C.type() == C_COM_POSITION) {
-    double c[3];
-    com_value(b, V, c);
-    for (int i = 0; i < 3; ++i) a += act.value2(i, c[i] - C.d()[i]);
-  } else if (C.type() == C_FRAME_VELOCITY) {
-    if (!vel) return 0.;
-    double r[6];
-    frame_velocity_res(b, V, C.d(), r);
-    for (int i = 0; i < 6; ++i) a += act.value2(i, r[i]);
-  } else {
-    double r[6] = {0., 0., 0., 0., 0., 0.};
-    const int nr = frame_residual_value(b, V, C, r);
-#pragma unroll
-    for (int i = 0; i < 6; ++i)  // fixed trip count: r stays in registers
-      if (i < nr) a += act.value2(i, r[i]);
-  }
-  return 0.5 * a;
-}
-
-// The long vector residuals (state, control) are summed lane-parallel in the calc:
-// wide_cost says which records (the first kMaxWide such records) take that path.
-constexpr int kMaxWide = 2;
-MB_HD __forceinline__ bool wide_cost(const CRec& C, int nwide) {
-  return (C.type() == C_STATE || C.type() == C_CONTROL) && nwide < kMaxWide;
-}
-// Lane l's share of twice the activation of a wide record: the rows i = l (mod L)
-// (lane 0 also the free-flyer block of a state residual, log6 of the base).
-MB_HD __forceinline__ double cost_activation_part(const Blk& b, const CRec& C, const double* x, const double* u,
-                                                  int nu, int l, int L) {
-  const Act act = cost_act(b, C, nu);
-  double a = 0.;
-  if (C.type() == C_STATE) {
-    const int ndx = 2 * b.nj, i0 = b.ff ? 6 : 0;
-    if (b.ff && l == 0) {
-      double Rr[9], pr[3], r[6];
-      ff_rel(C.d(), x, Rr, pr);
-      log6_t<double>(Rr, pr, r);
-      for (int e = 0; e < 6; ++e) a += act.value2(e, r[e]);
-    }
-    for (int i = i0 + l; i < ndx; i += L) a += act.value2(i, state_res(b, C.d(), x, i));
-  } else {
-    for (int i = l; i < nu; i += L) a += act.value2(i, u[i] - C.d()[i]);
-  }
-  return a;
-}
-
-// Cost value of the DAM (one thread; kinematics and velocities in V): sum of
-// weight * activation in record (name) order (cost-sum.hxx:89-117).
-MB_HD inline double cost_value(const Blk& b, const WVals& V, const double* x, const double* u, int nu) {
-  double total = 0.;
-  const double* cr = b.C;
-  for (int k = 0; k < b.ncost; ++k) {
-    const CRec C{cr};
-    total += C.weight() * cost_activation(b, V, C, x, u, nu);
-    cr += C.size();
-  }
-  return total;
-}
-
-// ---- contacts (ContactModel3D / 6D in the LOCAL frame) ----------------------
-// Row offset of contact record k and its record pointer.
-MB_HD inline const double* contact_rec(const Blk& b, int k, int* row0) {
-  const double* r = b.K;
-  int row = 0;
-  for (int i = 0; i < k; ++i) {
-    row += (int)r[0] == C_CONTACT_3D ? 3 : 6;
-    r += (int)r[3];
-  }
-  *row0 = row;
-  return r;
-}
-
-// a0 of a contact (contact-3d.hxx:35-43, contact-6d.hxx:31-44) in two parts,
-// so that neither holds log6 and the frame motions live at once: the
-// Baumgarte position term kp * (p - p_ref) | kp * log6(Mref^-1 oMf) (needs only
-// the placements), then the frame drift acceleration (classical for 3D, gravity
-// removed) + kd * v from the world velocity / acceleration of the body.
-MB_HD __attribute__((always_inline)) inline void contact_a0_position(const Blk& b, const WVals& W, const CRec& C, double* a0) {
-  const double kp = C.r[1];
-  double r[6] = {0., 0., 0., 0., 0., 0.};
-  if (kp != 0.) frame_residual_value(b, W, C, r);
-  const int n = C.type() == C_CONTACT_3D ? 3 : 6;
-#pragma unroll
-  for (int e = 0; e < 6; ++e)  // fixed trip count: r stays in registers
-    if (e < n) a0[e] = kp * r[e];
-}
-MB_HD __attribute__((always_inline)) inline void contact_a0_drift(const Blk& b, const WVals& W, const CRec& C, double* a0) {
-  const double* d = C.d();
-  const int j = frame_dof(b, d);
-  double Rf[9], pf[3], m6[6], vf[6], af[6];
-  frame_placement(b, W, d, Rf, pf);
-  for (int e = 0; e < 6; ++e) m6[e] = W.v(j)[e];
-  motion_act_inv(Rf, pf, m6, vf);
-  for (int e = 0; e < 6; ++e) m6[e] = W.a(j)[e] - W.root_a()[e];  // data.a has no gravity
-  motion_act_inv(Rf, pf, m6, af);
-  const double kd = C.r[2];
-  if (C.type() == C_CONTACT_3D) {
-    double wxv[3];
-    cross3(vf + 3, vf, wxv);
-    for (int e = 0; e < 3; ++e) a0[e] += af[e] + wxv[e] + kd * vf[e];
-  } else {
-    for (int e = 0; e < 6; ++e) a0[e] += af[e] + kd * vf[e];
-  }
-}
-
-// World force (at the origin) of contact record C for the multipliers lam
-// (updateForce: jMf.act(Force(lambda[, 0])), contact-3d.hxx:59-67).
-MB_HD inline void contact_world_force(const Blk& b, const WVals& W, const CRec& C, const double* lam, double* o) {
-  double Rf[9], pf[3], f[6];
-  frame_placement(b, W, C.d(), Rf, pf);
-  const bool c3 = C.type() == C_CONTACT_3D;
-  for (int e = 0; e < 6; ++e) f[e] = (c3 && e >= 3) ? 0. : lam[e];
-  force_act(Rf, pf, f, o);
-}
-
-// lane j < nj: sum of the contact forces acting on dof j's body (world) into fx[6j..]
-MB_HD inline void contact_joint_forces(const Blk& b, const WVals& W, const double* lam, double* fx, int j) {
-  double F[6] = {0., 0., 0., 0., 0., 0.};
-  const double* r = b.K;
-  int row = 0;
-  for (int k = 0; k < b.ncon; ++k) {
-    const CRec C{r};
-    if (frame_dof(b, C.d()) == j) {
-      double o[6];
-      contact_world_force(b, W, C, lam + row, o);
-      for (int e = 0; e < 6; ++e) F[e] += o[e];
-    }
-    row += C.type() == C_CONTACT_3D ? 3 : 6;
-    r += C.size();
-  }
-  for (int e = 0; e < 6; ++e) fx[6 * j + e] = F[e];
-}
-
-// lane c < nj: column c of the stacked contact Jacobian Jc (nc x nj,
-// Jc[row * nj + c]) — the LOCAL frame Jacobian (pinocchio getFrameJacobian LOCAL,
-// contact-3d.hxx:29 / contact-6d.hxx:29): the world motion S_c moved to the frame
-// (SE3::actInv of oMf), zero unless c moves the frame's body; with At != null also
-// into the columns [nj + row] of A (ld lda).
-MB_HD __attribute__((always_inline)) inline void contact_jac_lane(const Blk& b, const WVals& W, int c, double* Jc, double* At,
-                                                      int lda = 0) {
-  double Sc[6];
-  for (int e = 0; e < 6; ++e) Sc[e] = W.S(c)[e];
-  const double* r = b.K;
-  int row = 0;
-  for (int k = 0; k < b.ncon; ++k) {
-    const CRec C{r};
-    const int j = frame_dof(b, C.d());
-    double o[6] = {0., 0., 0., 0., 0., 0.};
-    if ((*W.anc(j) >> c) & 1ull) {
-      double Rf[9], pf[3];
-      frame_placement(b, W, C.d(), Rf, pf);
-      motion_act_inv(Rf, pf, Sc, o);
-    }
-    const int n = C.type() == C_CONTACT_3D ? 3 : 6;
-    for (int e = 0; e < n; ++e) {
-      Jc[(int64_t)(row + e) * b.nj + c] = o[e];
-      if (At) At[(int64_t)(b.nj + row + e) * lda + c] = o[e];
-    }
-    row += n;
-    r += C.size();
-  }
-}
 
 // Placements, world quantities, composite inertias and M (into A, zeroed by
 // the caller) for configuration q; `costs(wave, l)` runs on waves >= 1 in
@@ -2306,9 +208,6 @@ constexpr int kTreeKD = 16;  // depth bound of the device fast path (below)
 // (PR: nj x kTreeKD), the levels and descendant sets are wave ballots, and one wave-level
 // fence separates the levels. Same results as the generic steps up to the summation order
 // of a row's contributions.
-#ifndef MB_GJ_MARK
-#define MB_GJ_MARK(id)  // (tools/mb_probe: phase stamps)
-#endif
 typedef __attribute__((address_space(3))) Mask mb_lds_mask;
 typedef __attribute__((address_space(3))) int mb_lds_int;
 __device__ __forceinline__ void tree_wave_sync() {
@@ -2318,21 +217,16 @@ __device__ __forceinline__ void tree_wave_sync() {
 }
 // (the LDS operands arrive typed as LDS; the own row lives in registers during the
 // elimination, then L in the row's LDS copy, so only G's row is in registers after it)
-// (MB_TREE_NOINLINE builds it out of line: inlined into the rollout kernel at its
-// 256-VGPR cap, the register allocation trips the backend's "even aligned vector
-// registers" check; the rollout takes the dense solve instead, k_fwd.hip MB_CALC_DENSE.)
-#ifdef MB_TREE_NOINLINE
-#define MB_TREE_INL __attribute__((noinline))
-#else
-#define MB_TREE_INL __forceinline__
-#endif
+// (Inlined into the rollout kernel at its 256-VGPR cap it does not build: the register
+// allocation trips the backend's "even aligned vector registers" check. The rollout takes
+// the dense solve instead, k_fwd.hip MB_CALC_DENSE.)
 __device__ __forceinline__ Mask readlane_mask(Mask v, int l) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
   const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
   return (Mask(hi) << 32) | lo;
 }
-__device__ MB_TREE_INL void tree_ltdl_wave(const mb_lds_mask* anc, int ff, int nj, mb_lds_d* A, int lda,
-                                           int md, mb_lds_d* PR, mb_lds_d* dinv_out, mb_lds_int* bad_out) {
+__device__ __forceinline__ void tree_ltdl_wave(const mb_lds_mask* anc, int ff, int nj, mb_lds_d* A, int lda, int md,
+                                               mb_lds_d* PR, mb_lds_d* dinv_out, mb_lds_int* bad_out) {
   // Written for the instruction stream of one wave: every register array index is static
   // (the levels are unrolled, so level L touches only the path entries s < L), the
   // level's dofs are a uniform (scalar) loop with their rows read as LDS broadcasts, and
@@ -2595,7 +489,6 @@ template <class X, class Side = TreeNoSide>
 MB_HD __forceinline__ void tree_ltdl(const X& ex, const Blk& b, const WVals& W, double* A, int lda, const TreeWork& tw,
                                      int md, double* PR, Side side = Side{}, int nslots = 0, int* ctr = nullptr) {
 #if defined(__HIP_DEVICE_COMPILE__)
-#ifndef MB_TREE_NO_WAVE
   if (md < kTreeKD) {
     double* const Al = ex.lds(A);
     double* const PRl = ex.lds(PR);
@@ -2614,7 +507,6 @@ MB_HD __forceinline__ void tree_ltdl(const X& ex, const Blk& b, const WVals& W, 
     });
     return;
   }
-#endif
 #endif
   (void)PR;
   tree_ltdl_steps(ex, b, W, A, lda, tw, md);
@@ -2788,14 +680,10 @@ MB_HD inline int64_t calc_work_doubles(int nj, int nc = 0) {
 // The calc's cost records other than the wide ones (knot_calc_x): record item i on lane
 // i / 3 of side wave i % 3 (sl: the lane counted from the first side wave, snt: the side
 // lanes), each record's weighted value into cv[k]. It rebuilds the block's views from the
-// LDS pointers, so it can be built out of line (MB_TREE_NOINLINE, as tree_ltdl_wave).
-#if defined(__HIP_DEVICE_COMPILE__) && defined(MB_TREE_NOINLINE)
-__device__ __attribute__((noinline))
-#else
-MB_HD __forceinline__
-#endif
-void calc_cost_records(const double* P_, double* w_, double* parts_, const double* x_, const double* ub_, double* cv_,
-                       int sl, int snt) {
+// LDS pointers. (With tree_ltdl_wave it is inlined into knot_calc_x, which therefore does not
+// build at the rollout's register cap: the rollout runs knot_calc_dense_x.)
+MB_HD __forceinline__ void calc_cost_records(const double* P_, double* w_, double* parts_, const double* x_,
+                                             const double* ub_, double* cv_, int sl, int snt) {
   const double* P = mb_lds(P_);
   const Blk b = parse_uniform(P);
   const WVals W{mb_lds(w_), b.nj, mb_lds(parts_)};
@@ -3907,16 +1795,6 @@ typedef __attribute__((address_space(1))) double mb_glb_d;
 #else
 #define MB_MFMA_UNIFORM(x)
 #endif
-// (tools/mb_probe: cycles of thread 0 inside the tile loops, summed over its tiles in
-// registers: MB_TILE_LAP(k) adds the time since the last lap to sum k, after the operands
-// named in MB_TILE_PIN have arrived; MB_TILE_FLUSH(base) stores the sums and the tile count)
-#ifndef MB_TILE_DECL
-#define MB_TILE_DECL
-#define MB_TILE_START(n)
-#define MB_TILE_PIN4(a)
-#define MB_TILE_LAP(k)
-#define MB_TILE_FLUSH(base)
-#endif
 // The Fx block (euler.hxx:100-112 with JintegrateTransport / Jintegrate;
 // impulse-fwddyn.hxx:111-115) straight from the da product's accumulators:
 // da = -(Kinv_tl dtau + H da0) (contact-fwddyn.hxx:127-140 as computeABADerivatives / the
@@ -4857,7 +2735,7 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
         const int e = e0 + u * ex.nt;
         if (e >= ne) break;
         Rm[e] = v4[u];
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MB_NO_MFMA_GN)
+#if defined(__HIP_DEVICE_COMPILE__)
         // the matrix-core GEMM takes each row's weight times its activation Hessian (w h)
         if (e % ldR == 0) {
           const int row = e / ldR;
@@ -4867,7 +2745,7 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
 #endif
       }
     }
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MB_NO_MFMA_GN)
+#if defined(__HIP_DEVICE_COMPILE__)
     // the diagonal terms of the state / control costs (beyond the free-flyer block), per
     // column of [x tangent | u], in cost order
     for (int i = lane; i < L + m; i += ex.nt) {
@@ -4899,7 +2777,7 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
     const double* const P = ex.lds(P_);
     const double* const x = ex.lds(x_);
     const double* const u = ex.lds(u_);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MB_NO_MFMA_GN)
+#if defined(__HIP_DEVICE_COMPILE__)
     gn_blocks_mfma(Rm, ldR, ch, nrows, L, nu, m, sc, Lxx, Lxu, Luu, cdg_);
     MB_GJ_MARK(26);
 #else

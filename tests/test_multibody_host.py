@@ -4,6 +4,7 @@ numpy oracle (oracle/multibody_np.py: ABA + complex-step derivatives). CPU
 only: the same arithmetic the GPU runs, checked without a GPU (the GPU run of
 it is tests/test_multibody_gpu.py)."""
 import ctypes as C
+import glob
 import os
 import subprocess
 
@@ -21,7 +22,9 @@ D = C.POINTER(C.c_double)
 
 @pytest.fixture(scope="module")
 def lib():
-    hdrs = [os.path.join(ROOT, "crocoddyl_amd", "csrc", h) for h in ("multibody.hpp", "launch_plan.hpp")]
+    # every kernel header: mb_host.cpp reaches most of them through launch_plan.hpp
+    hdrs = glob.glob(os.path.join(ROOT, "crocoddyl_amd", "csrc", "*.hpp"))
+    hdrs.append(os.path.join(ROOT, "include", "fddp_hip.h"))
     if not os.path.exists(OUT) or os.path.getmtime(OUT) < max(map(os.path.getmtime, [SRC] + hdrs)):
         os.makedirs(os.path.dirname(OUT), exist_ok=True)
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O2", "-std=c++17",

@@ -34,8 +34,10 @@ def host_run(blk, nx, nu, mm, x, u):
     import subprocess
     src = os.path.join(ROOT, "tests", "cpp", "mb_host.cpp")
     out = os.path.join(ROOT, "tests", "_build", "libmb_host.so")
-    hdr = os.path.join(ROOT, "crocoddyl_amd", "csrc", "multibody.hpp")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+    import glob
+    hdrs = glob.glob(os.path.join(ROOT, "crocoddyl_amd", "csrc", "*.hpp"))
+    hdrs.append(os.path.join(ROOT, "include", "fddp_hip.h"))
+    if not os.path.exists(out) or os.path.getmtime(out) < max(map(os.path.getmtime, [src] + hdrs)):
         os.makedirs(os.path.dirname(out), exist_ok=True)
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O2", "-std=c++17",
                                "-shared", "-fPIC", "-o", out, src])
