@@ -139,9 +139,9 @@ int check_knots(const fddp_dims& d, const fddp_knot_desc* knots, const double* p
       const int nb = k.param_stride > 0 ? d.B : 1;
       for (int b = 0; b < nb; ++b) {
         const int64_t off = k.param_offset + (int64_t)b * k.param_stride;
-        std::string why;
+        plan::Refusal why;
         const int64_t s1 = mb_block_check(params + off, n_params - off, k.kind, d.nx, k.nu, why, nullptr, nullptr, nullptr);
-        if (s1 < 0) return fail(FDDP_ERR_INVALID_ARG, w + ": knot " + std::to_string(t) + ": " + why);
+        if (s1 < 0) return fail(FDDP_ERR_INVALID_ARG, w + ": knot " + std::to_string(t) + ": " + why.str());
         if (k.param_stride > 0 && s1 > k.param_stride)
           return fail(FDDP_ERR_INVALID_ARG, w + ": knot " + std::to_string(t) + " blocks overlap (stride too small)");
         sz = std::max(sz, s1);

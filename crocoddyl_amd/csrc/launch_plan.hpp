@@ -100,11 +100,19 @@ inline int64_t block_doubles(int kind, int nx, int nu) {
   return -1;
 }
 
+// Why a parameter block is refused: a literal, and the number of an unknown record type.
+struct Refusal {
+  const char* text = nullptr;
+  int type = -1;
+  Refusal& operator=(const char* s) { return text = s, *this; }
+  std::string str() const { return type < 0 ? std::string(text) : text + (" " + std::to_string(type)); }
+};
+
 // Checks one FDDP_KNOT_EULER_FREEFWD / _CONTACTFWD / FDDP_KNOT_IMPULSEFWD block
 // (layouts in include/fddp_hip.h) against nx / nu and the space left in the
 // pool. Returns its size in doubles, or -1 with `why` set. nj / njac / nc:
 // dofs, jac costs and contact rows (LDS sizing).
-inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, int nu, std::string& why, int* nj_out,
+inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, int nu, Refusal& why, int* nj_out,
                               int* njac_out, int* nc_out, bool* vcols_out = nullptr, int* nu_out = nullptr,
                               int* nrows_out = nullptr) {
   using namespace fddp::mb;
@@ -157,13 +165,15 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
     if (type == C_CONTROL) want = kCHdr + nu + ap * (int64_t)nu;
     if (type == C_FRAME_PLACEMENT) want = kCHdr + 25 + ap * 6;
     if (type == C_FRAME_TRANSLATION) want = kCHdr + 16 + ap * 3;
+    if (type == C_FRAME_ROTATION) want = kCHdr + 22 + ap * 3;
     if (type == C_FRAME_VELOCITY) {
       if (impulse) return why = "frame-velocity costs are covered on Euler knots only", -1;
       want = kCHdr + 19 + ap * 6;
     }
     if (type == C_COM_POSITION) want = kCHdr + 3 + ap * 3;
-    if (type == C_CONTACT_FORCE || type == C_FRICTION_CONE) {
-      // [row0, nr, fref(6)] | [row0, nc, nr, A(3 nr)]; rows checked against the contacts below
+    if (type == C_CONTACT_FORCE || type == C_FRICTION_CONE || type == C_COP_POSITION) {
+      // [row0, nr, fref(6)] | [row0, nc, nr, A(3 nr)] | [row0, nc, nr, A(6 nr)]; rows checked against the
+      // contacts below
       if (kind != FDDP_KNOT_EULER_CONTACTFWD) return why = "force costs need contact knots", -1;
       if (o + kCHdr + 3 > size) return why = "cost records out of range", -1;
       const int row0 = (int)C[kCHdr];
@@ -174,6 +184,12 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
         if (nrf != 3 && nrf != 6) return why = "contact-force costs need a 3- or 6-row force", -1;
         want = kCHdr + 8 + ap * nrf;
         if (row0 >= 0) force_rows = std::max(force_rows, row0 + nrf);
+      } else if (type == C_COP_POSITION) {
+        const int ncc = (int)C[kCHdr + 1], nrc = (int)C[kCHdr + 2];
+        if ((double)nrc != C[kCHdr + 2] || nrc < 1 || nrc > 6) return why = "CoP support rows out of [1, 6]", -1;
+        if (row0 >= 0 && ncc != 6) return why = "CoP position cost on a contact of 6 rows", -1;
+        want = kCHdr + 3 + 6 * nrc + ap * nrc;
+        if (row0 >= 0) force_rows = std::max(force_rows, row0 + ncc);
       } else {
         const int ncc = (int)C[kCHdr + 1], nrc = (int)C[kCHdr + 2];
         if ((double)nrc != C[kCHdr + 2] || nrc < 1 || nrc > 6) return why = "friction cone rows out of [1, 6]", -1;
@@ -182,9 +198,10 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
         if (row0 >= 0) force_rows = std::max(force_rows, row0 + ncc);
       }
     }
-    if (want < 0) return why = "unknown cost type " + std::to_string(type), -1;
+    if (want < 0) return why = "unknown cost type", why.type = type, -1;
     if (rs != want || o + rs > size) return why = "cost record of the wrong size", -1;
-    if (type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_FRAME_VELOCITY) {
+    if (type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_FRAME_VELOCITY ||
+        type == C_FRAME_ROTATION) {
       const int fj = (int)C[kCHdr];
       if ((double)fj != C[kCHdr] || fj < 0 || fj >= nb) return why = "frame attached to an unknown joint", -1;
     }
@@ -192,7 +209,7 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
       for (int e = 0; e < 7; ++e)
         if (!std::isfinite(C[kCHdr + e])) return why = "non-finite reference state", -1;
     if (type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_COM_POSITION ||
-        type == C_FRAME_VELOCITY || (type == C_STATE && ff))
+        type == C_FRAME_VELOCITY || type == C_FRAME_ROTATION || (type == C_STATE && ff))
       ++njac;
     if (type == C_FRAME_VELOCITY) vcols = true;
     o += rs;
@@ -223,7 +240,7 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
       int64_t want = -1;
       if (type == C_CONTACT_3D) want = kCHdr + (impulse ? 13 : 16);
       if (type == C_CONTACT_6D) want = kCHdr + (impulse ? 13 : 25);
-      if (want < 0) return why = "unknown contact type " + std::to_string(type), -1;
+      if (want < 0) return why = "unknown contact type", why.type = type, -1;
       if (rs != want || o + rs > size) return why = "contact record of the wrong size", -1;
       const int fj = (int)C[kCHdr];
       if ((double)fj != C[kCHdr] || fj < 0 || fj >= nb) return why = "contact frame attached to an unknown joint", -1;
@@ -240,7 +257,8 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
     int64_t oc = FDDP_PARAM_HEADER + 3 + nj + (int64_t)kJRec * nb;
     for (int k = 0; k < ncost; ++k) {
       const double* C = P + oc;
-      if (((int)C[0] == C_CONTACT_FORCE || (int)C[0] == C_FRICTION_CONE) && (int)C[kCHdr] >= 0) {
+      if (((int)C[0] == C_CONTACT_FORCE || (int)C[0] == C_FRICTION_CONE || (int)C[0] == C_COP_POSITION) &&
+          (int)C[kCHdr] >= 0) {
         bool hit = false;
         for (const auto& r : crow) hit = hit || (r.first == (int)C[kCHdr] && r.second == (int)C[kCHdr + 1]);
         if (!hit) return why = "a force cost must read one whole contact of its size", -1;
@@ -264,7 +282,9 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
 }
 
 // The LDS plans, the fast-path choice and the initial trial-group size of a knot sequence
-// (validated by fddp_hip.hip check_knots).
+// (validated by fddp_hip.hip check_knots, which refuses a bad block before the library
+// plans; a host caller that plans unchecked knots gets the first block refusal's text as
+// the plan's error, unless the plan itself is refused first).
 inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const double* params, int64_t n_params,
                         const Overrides& ov) {
   using ktab::kNT;
@@ -284,6 +304,7 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
     bool vcols;
   };
   std::vector<MbShape> shapes;
+  const char* refused = nullptr;  // the first block refusal
   p.all_mb = true;
   for (int t = 0; t <= d.T; ++t) {
     int64_t sz;
@@ -293,11 +314,16 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
       const int nb = knots[t].param_stride > 0 ? d.B : 1;
       for (int b = 0; b < nb; ++b) {
         const int64_t off = knots[t].param_offset + (int64_t)b * knots[t].param_stride;
-        std::string why;
+        Refusal why;
         MbShape k{0, 0, 0, 0, 0, false};
-        sz = std::max(sz, mb_block_check(params + off, n_params - off, knots[t].kind, d.nx, knots[t].nu, why, &k.nj,
-                                         &k.njac, &k.nc, &k.vcols, &k.nu, &k.nrows));
-        mb_pmax = std::max<int64_t>(mb_pmax, (int64_t)params[off + 3]);
+        const int64_t s1 = mb_block_check(params + off, n_params - off, knots[t].kind, d.nx, knots[t].nu, why, &k.nj,
+                                          &k.njac, &k.nc, &k.vcols, &k.nu, &k.nrows);
+        if (s1 < 0 && !refused) refused = why.text;
+        // (a refused block is planned with its size field, as mb_pmax is: the budget below
+        // then refuses only what is over it)
+        const int64_t own = (int64_t)params[off + 3];
+        sz = std::max(sz, s1 < 0 ? own : s1);
+        mb_pmax = std::max<int64_t>(mb_pmax, own);
         mb_nj = std::max(mb_nj, k.nj);
         mb_njac = std::max(mb_njac, k.njac);
         mb_nc = std::max(mb_nc, k.nc);
@@ -373,6 +399,7 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
   p.uniform_nu = p.uniform_nu || (p.all_mb && d.nu_max > 0);
   p.ntl = (d.ndx + 15) / 16;
   p.mtl = (d.nu_max + 15) / 16;
+  if (refused) p.error = refused;
   return p;
 }
 

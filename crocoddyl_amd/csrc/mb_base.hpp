@@ -120,7 +120,10 @@ enum {
   C_COM_POSITION = 8,   // r = com(q) - cref: payload [cref(3)] (com-position.hxx:49-75)
   C_FRICTION_CONE = 9,  // r = A lambda_lin: payload [row0, nc, nr, A (nr x 3 row-major)]
                         // (contact-friction-cone.hxx:51-91)
-  C_FRAME_VELOCITY = 10  // r = LOCAL frame velocity - vref: frame payload + vref(6) (frame-velocity.hxx:53-84)
+  C_FRAME_VELOCITY = 10,  // r = LOCAL frame velocity - vref: frame payload + vref(6) (frame-velocity.hxx:53-84)
+  C_COP_POSITION = 11,    // r = A lambda of a 6D contact: payload [row0, nc, nr, A (nr x 6 row-major)]
+                          // (contact-cop-position.hpp)
+  C_FRAME_ROTATION = 12   // r = log3(Rref^T oRf): frame payload + Rref^T (9) (frame-rotation.hxx)
 };
 // Activation of a cost record: header slot 2 (core/activations/*.hpp)
 enum { A_QUAD = 0, A_WEIGHTED_QUAD = 1, A_QUAD_BARRIER = 2, A_WEIGHTED_QUAD_BARRIER = 3 };

@@ -32,7 +32,8 @@ MB_HD inline void frame_placement(const Blk& b, const WVals& V, const double* d,
 
 // Residual of a frame cost and, with S != null (the world motion of a dof that
 // moves the frame), its Jacobian column. Returns the residual size (6 placement,
-// 3 translation).
+// 3 translation, 3 rotation: log3(Rref^T oRf), the angular half of log6 with no
+// translation, so that Jc is Jlog3(r) times the frame's LOCAL angular Jacobian column).
 MB_HD inline int frame_residual(const Blk& b, const WVals& V, const CRec& C, const double* S, double* r, double* Jc) {
   const double* d = C.d();
   double Rf[9], pf[3];
@@ -57,8 +58,12 @@ MB_HD inline int frame_residual(const Blk& b, const WVals& V, const CRec& C, con
     return 3;
   }
   // rMf = Mref^-1 oMf
+  // a rotation cost: the same log6 on (Rref^T oRf, 0), whose linear half is zero and whose
+  // angular half is log3 (one instance of log6_t in the kernel); its record has no
+  // translation slot, so pr, unused then, adds three elements of Rref^T instead
+  const bool rot = C.type() == C_FRAME_ROTATION;
   const double* Rri = d + 13;
-  const double* pri = d + 22;
+  const double* pri = rot ? d + 13 : d + 22;
   double Rr[9], pr[3], dRr[9], dpr[3];
   matmul3(Rri, Rf, Rr);
   matvec3(Rri, pf, pr);
@@ -69,20 +74,23 @@ MB_HD inline int frame_residual(const Blk& b, const WVals& V, const CRec& C, con
   matvec3(Rri, dp, dpr);
   Dual RD[9], PD[3], o[6];
   for (int e = 0; e < 9; ++e) RD[e] = Dual{Rr[e], dRr[e]};
-  for (int e = 0; e < 3; ++e) PD[e] = Dual{pr[e], dpr[e]};
+  for (int e = 0; e < 3; ++e) PD[e] = rot ? Dual{0., 0.} : Dual{pr[e], dpr[e]};
   log6_t<Dual>(RD, PD, o);
-  for (int e = 0; e < 6; ++e) {
-    r[e] = o[e].v;
-    if (Jc) Jc[e] = S ? o[e].d : 0.;
+  for (int e = 0; e < 3; ++e) {
+    const Dual lo = rot ? o[3 + e] : o[e], hi = rot ? Dual{0., 0.} : o[3 + e];
+    r[e] = lo.v;
+    r[3 + e] = hi.v;
+    if (Jc) Jc[e] = S ? lo.d : 0.;
+    if (Jc) Jc[3 + e] = S ? hi.d : 0.;
   }
-  return 6;
+  return rot ? 3 : 6;
 }
 
 // Residual size of a cost record.
 MB_HD inline int cost_nr(const Blk& b, const CRec& C, int nu) {
   const int t = C.type();
   if (t == C_CONTACT_FORCE) return (int)C.d()[1];
-  if (t == C_FRICTION_CONE) return (int)C.d()[2];
+  if (t == C_FRICTION_CONE || t == C_COP_POSITION) return (int)C.d()[2];
   if (t == C_STATE) return 2 * b.nj;
   if (t == C_CONTROL) return nu;
   return (t == C_FRAME_PLACEMENT || t == C_FRAME_VELOCITY) ? 6 : 3;
@@ -130,10 +138,10 @@ MB_HD inline Act cost_act(const Blk& b, const CRec& C, int nu) {
 // block of a state cost
 MB_HD __forceinline__ bool jac_cost(const Blk& b, int type) {
   return type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_COM_POSITION ||
-         type == C_FRAME_VELOCITY || (type == C_STATE && b.ff);
+         type == C_FRAME_VELOCITY || type == C_FRAME_ROTATION || (type == C_STATE && b.ff);
 }
 MB_HD __forceinline__ int jac_rows(int type) {
-  return (type == C_FRAME_TRANSLATION || type == C_COM_POSITION) ? 3 : 6;
+  return (type == C_FRAME_TRANSLATION || type == C_COM_POSITION || type == C_FRAME_ROTATION) ? 3 : 6;
 }
 MB_HD inline int count_jac_costs(const Blk& b, bool* vel_cols = nullptr) {
   int n = 0;
@@ -148,8 +156,14 @@ MB_HD inline int count_jac_costs(const Blk& b, bool* vel_cols = nullptr) {
   if (vel_cols) *vel_cols = fv;
   return n;
 }
-// costs on the contact multipliers: CostModelContactForce, CostModelContactFrictionCone
-MB_HD __forceinline__ bool force_cost(int type) { return type == C_CONTACT_FORCE || type == C_FRICTION_CONE; }
+// costs on the contact multipliers: CostModelContactForce, CostModelContactFrictionCone,
+// CostModelContactCoPPosition
+MB_HD __forceinline__ bool force_cost(int type) {
+  return type == C_CONTACT_FORCE || type == C_FRICTION_CONE || type == C_COP_POSITION;
+}
+// columns of the matrix A of a cone / CoP record: the multipliers its rows read (the
+// linear three of the contact, or the whole wrench of a 6D one)
+MB_HD __forceinline__ int force_cols(int type) { return type == C_COP_POSITION ? 6 : 3; }
 // Residual rows with a dense Jacobian (jac costs; force costs on an active contact
 // when the force Jacobians are computed): the rows of the stacked R of calcDiff.
 MB_HD inline int count_cost_rows(const Blk& b, int nu) {
@@ -168,6 +182,8 @@ MB_HD inline int count_cost_rows(const Blk& b, int nu) {
 // [row0, row0 + nc) (lam unread for an inactive contact: lambda = 0):
 //   contact force: lambda_i - fref_i (contact-force.hxx:33-50: jMf.actInv(f) is the multiplier);
 //   friction cone: A_i . lambda_lin (contact-friction-cone.hxx:58)
+//   CoP position: A_i . lambda (contact-cop-position.hpp), the cone's sum carried on
+//     over the three torque multipliers
 // (lam(k): multiplier k, so that the calc reads it where it lies, sign applied at the use)
 template <class L>
 MB_HD __forceinline__ double force_res_at(const CRec& C, L lam, int i) {
@@ -175,8 +191,11 @@ MB_HD __forceinline__ double force_res_at(const CRec& C, L lam, int i) {
   const int row0 = (int)d[0];
   if (C.type() == C_CONTACT_FORCE) return (row0 >= 0 ? lam(row0 + i) : 0.) - d[2 + i];
   if (row0 < 0) return 0.;
-  const double* A = d + 3 + 3 * i;
-  return A[0] * lam(row0) + A[1] * lam(row0 + 1) + A[2] * lam(row0 + 2);
+  const int nw = force_cols(C.type());
+  const double* A = d + 3 + nw * i;
+  double s = A[0] * lam(row0) + A[1] * lam(row0 + 1) + A[2] * lam(row0 + 2);
+  for (int k = 3; k < nw; ++k) s += A[k] * lam(row0 + k);
+  return s;
 }
 MB_HD __forceinline__ double force_res(const CRec& C, const double* lam, int i) {
   return force_res_at(C, [lam](int k) { return lam[k]; }, i);
@@ -187,8 +206,11 @@ MB_HD __forceinline__ double force_jac(const CRec& C, const double* dl, int64_t 
   const double* d = C.d();
   const int row0 = (int)d[0];
   if (C.type() == C_CONTACT_FORCE) return dl[(int64_t)(row0 + i) * ld];
-  const double* A = d + 3 + 3 * i;
-  return A[0] * dl[(int64_t)row0 * ld] + A[1] * dl[(int64_t)(row0 + 1) * ld] + A[2] * dl[(int64_t)(row0 + 2) * ld];
+  const int nw = force_cols(C.type());
+  const double* A = d + 3 + nw * i;
+  double s = A[0] * dl[(int64_t)row0 * ld] + A[1] * dl[(int64_t)(row0 + 1) * ld] + A[2] * dl[(int64_t)(row0 + 2) * ld];
+  for (int k = 3; k < nw; ++k) s += A[k] * dl[(int64_t)(row0 + k) * ld];
+  return s;
 }
 // activation value of a force cost (inactive contact: lambda = 0)
 template <class L>
@@ -213,6 +235,12 @@ MB_HD __forceinline__ int frame_residual_value(const Blk& b, const WVals& V, con
   }
   double Rr[9], pr[3];
   matmul3(d + 13, Rf, Rr);
+  if (C.type() == C_FRAME_ROTATION) {  // log3(Rref^T oRf): log6's angular half, no translation
+    for (int e = 0; e < 3; ++e) pr[e] = 0.;
+    log6_t<double>(Rr, pr, r);
+    for (int e = 0; e < 3; ++e) r[e] = r[3 + e];
+    return 3;
+  }
   matvec3(d + 13, pf, pr);
   for (int e = 0; e < 3; ++e) pr[e] += d[22 + e];
   log6_t<double>(Rr, pr, r);

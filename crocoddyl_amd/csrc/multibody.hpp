@@ -1696,7 +1696,7 @@ MB_HD inline void jac_lane(const Blk& b, const WVals& W, const double* x, int j,
       ++f;
     } else if (jac_cost(b, t)) {
       double r[6] = {0., 0., 0., 0., 0., 0.}, Jc[6] = {0., 0., 0., 0., 0., 0.};
-      if (t == C_FRAME_PLACEMENT || t == C_FRAME_TRANSLATION) {
+      if (t == C_FRAME_PLACEMENT || t == C_FRAME_TRANSLATION || t == C_FRAME_ROTATION) {
         const bool sup = (*W.anc(frame_dof(b, C.d())) >> j) & 1ull;
         frame_residual(b, W, C, sup ? S : nullptr, r, Jc);
       } else if (t == C_FRAME_VELOCITY) {  // getFrameVelocityDerivatives (LOCAL)

@@ -46,9 +46,12 @@ def _geom_q(x0, nq):
 
 
 class SimpleBipedGaitProblem:
-    """Defines a simple 3d locomotion problem (utils/biped.py:6-308)."""
+    """Defines a simple 3d locomotion problem (utils/biped.py:6-308). ``copSupport`` =
+    (L, W), the feet's extent along their frames' x and y, adds a
+    CostModelContactCoPPosition (weight ``copWeight``) on every support foot, as the
+    reference fork's humanoid walks do (contact-cop-position.hpp); None: no such cost."""
 
-    def __init__(self, rmodel, rightFoot, leftFoot):
+    def __init__(self, rmodel, rightFoot, leftFoot, copSupport=None, copWeight=1e1):
         self.rmodel = rmodel
         self.state = mb.StateMultibody(self.rmodel)
         self.actuation = mb.ActuationModelFloatingBase(self.state)
@@ -59,6 +62,8 @@ class SimpleBipedGaitProblem:
         self.firstStep = True
         self.mu = 0.7
         self.nsurf = np.array([0., 0., 1.])
+        self.copSupport = None if copSupport is None else np.array(copSupport, float).reshape(2)
+        self.copWeight = float(copWeight)
 
     def createWalkingModels(self, x0, stepLength, stepHeight, timeStep, stepKnots, supportKnots):
         """The running models of createWalkingProblem (biped.py:25-65)."""
@@ -164,6 +169,10 @@ class SimpleBipedGaitProblem:
                 self.state, mb.ActivationModelQuadraticBarrier(mb.ActivationBounds(cone.lb, cone.ub)),
                 mb.FrameFrictionCone(i, cone), self.actuation.nu)
             costModel.addCost(self.rmodel.frames[i][0] + "_frictionCone", frictionCone, 1e1)
+            if self.copSupport is not None:
+                copCost = mb.CostModelContactCoPPosition(self.state, mb.FrameCoPSupport(i, self.copSupport),
+                                                         self.actuation.nu)
+                costModel.addCost(self.rmodel.frames[i][0] + "_CoP", copCost, self.copWeight)
 
     def _contacts6d(self, supportFootIds):
         contactModel = mb.ContactModelMultiple(self.state, self.actuation.nu)

@@ -13,8 +13,10 @@ Reference API mirrored:
   CostModelSum(state, nu).addCost(name, cost, weight)   multibody/costs/cost-sum.hxx:18-85
   CostModelState / CostModelControl / CostModelFramePlacement / CostModelFrameTranslation
   / CostModelCoMPosition / CostModelContactForce / CostModelContactFrictionCone
+  / CostModelContactCoPPosition / CostModelFrameRotation
                                                 multibody/costs/*.hxx
-  FramePlacement(id, SE3), FrameTranslation(id, p)      multibody/frames.hpp
+  FramePlacement(id, SE3), FrameTranslation(id, p), FrameRotation(id, R),
+  FrameCoPSupport(id, support_region)           multibody/frames.hpp
   DifferentialActionModelFreeFwdDynamics(state, actuation, costs)  .armature
                                                 multibody/actions/free-fwddyn.hxx:24-160
 Pinocchio is not available offline, so ``RobotModel`` stands in for
@@ -38,6 +40,8 @@ COST_CONTACT_FORCE = 7
 COST_COM_POSITION = 8
 COST_FRICTION_CONE = 9
 COST_FRAME_VELOCITY = 10
+COST_COP_POSITION = 11
+COST_FRAME_ROTATION = 12
 MAX_CONTACT_ROWS = 24
 MAX_DOFS = 64  # nv of the device path (one lane per tangent direction of a wave pair)
 
@@ -795,6 +799,40 @@ class FrameTranslation:
         self.translation = np.array(translation, np.float64)
 
 
+class FrameRotation:
+    """FrameRotation(id, rotation) (multibody/frames.hpp): frame id and a 3 x 3 rotation."""
+
+    def __init__(self, id, rotation):
+        self.id = int(id)
+        self.rotation = np.array(rotation, np.float64)
+        if self.rotation.shape != (3, 3):
+            raise ValueError("Invalid argument: rotation has wrong dimension (it should be 3 x 3)")
+
+
+class FrameCoPSupport:
+    """FrameCoPSupport(id, support_region) (multibody/frames.hpp of the reference fork):
+    the foot's extent (L, W) along the contact frame's x and y, centred on the frame
+    origin. ``A`` (4 x 6) acts on the wrench (fx, fy, fz, tx, ty, tz): with the centre of
+    pressure (-ty / fz, tx / fz), A f >= 0 keeps it inside the region for fz > 0."""
+
+    def __init__(self, id, support_region):
+        self.id = int(id)
+        self.update_A(support_region)
+
+    def update_A(self, support_region):
+        box = np.array(support_region, np.float64).reshape(-1)
+        if box.size != 2:
+            raise ValueError("Invalid argument: support_region has wrong dimension (it should be 2)")
+        if not (box > 0.0).all():
+            raise ValueError("Invalid argument: the support region's extents have to be positive")
+        self.support_region = box
+        L, W = box
+        self.A = np.array([[0.0, 0.0, L / 2, 0.0, -1.0, 0.0],
+                           [0.0, 0.0, L / 2, 0.0, 1.0, 0.0],
+                           [0.0, 0.0, W / 2, 1.0, 0.0, 0.0],
+                           [0.0, 0.0, W / 2, -1.0, 0.0, 0.0]])
+
+
 class _Cost:
     """CostModelAbstract (multibody/cost-base.hxx): state, activation, nu."""
 
@@ -924,6 +962,30 @@ class CostModelFrameTranslation(_Cost):
         return [frame, _rows(self.xref.translation, 3)]
 
 
+class CostModelFrameRotation(_Cost):
+    """r = log3(Rref^T oRf) (frame-rotation.hxx): Rx = [Jlog3(r) fJf_angular, 0], Ru = 0.
+    Overloads (state, activation, Rref[, nu]) and (state, Rref[, nu]). Parity unpinned
+    against the reference binary."""
+
+    type = COST_FRAME_ROTATION
+
+    def __init__(self, state, *args, **kw):
+        act, ref, nu = _cost_args(args, kw)
+        ref = kw.get("Rref", ref)
+        if not isinstance(ref, FrameRotation):
+            raise TypeError("CostModelFrameRotation needs a FrameRotation reference")
+        super().__init__(state, act, 3, nu)
+        self.Rref = ref
+
+    def _payload(self):  # frame, then Rref^T in the order the placement record keeps Mref^-1's rotation
+        model = self.state.pinocchio
+        name, pj, pl = model.frames[self.Rref.id]
+        if pj == 0:
+            raise ValueError("Invalid argument: frames attached to the universe are not supported")
+        frame = np.concatenate([[pj - 1], pl.rotation.T.reshape(-1), pl.translation]).reshape(1, -1)
+        return [frame, np.array(self.Rref.rotation.reshape(-1)).reshape(1, -1)]
+
+
 class CostModelCoMPosition(_Cost):
     """r = com(q) - cref (com-position.hxx:49-75): Rx = [Jcom, 0]."""
 
@@ -1030,6 +1092,45 @@ class CostModelContactFrictionCone(_Cost):
 
     def _payload(self):  # [row0 (resolved by the DAM), contact rows, nr, A (nr x 3, row-major)]
         A = self.fref.cone.A
+        return [np.concatenate([[-1.0, 0.0, A.shape[0]], A.reshape(-1)]).reshape(1, -1)]
+
+
+class CostModelContactCoPPosition(_Cost):
+    """r = A lambda (contact-cop-position.hpp of the reference fork): the support matrix
+    of cop_support times the six multipliers of the ContactModel6D on frame
+    cop_support.id, the multiplier CostModelContactForce reads. Overloads
+    (state, activation, cop_support[, nu]) and (state, cop_support[, nu]) with
+    ActivationModelQuadraticBarrier(ActivationBounds(zeros(4), DBL_MAX ones(4))) by
+    default. Its derivatives are A d lambda / dx (du), which the DAM computes only with
+    enable_force=True (zero otherwise). Parity unpinned against the reference binary."""
+
+    type = COST_COP_POSITION
+
+    def __init__(self, state, *args, **kw):
+        act = ref = nu = None
+        for a in args:
+            if isinstance(a, _ACTIVATIONS):
+                act = a
+            elif isinstance(a, FrameCoPSupport):
+                ref = a
+            elif isinstance(a, (int, np.integer)) and not isinstance(a, bool):
+                nu = int(a)
+        act = kw.get("activation", act)
+        ref = kw.get("cop_support", ref)
+        nu = kw.get("nu", nu)
+        if not isinstance(ref, FrameCoPSupport):
+            raise TypeError("CostModelContactCoPPosition needs a FrameCoPSupport reference")
+        if act is None:
+            act = ActivationModelQuadraticBarrier(ActivationBounds(np.zeros(4), np.full(4, DBL_MAX)))
+        super().__init__(state, act, 4, nu)
+        self.cop_support = ref
+
+    @property
+    def frame_id(self):
+        return self.cop_support.id
+
+    def _payload(self):  # [row0 (resolved by the DAM), contact rows, nr, A (nr x 6, row-major)]
+        A = self.cop_support.A
         return [np.concatenate([[-1.0, 0.0, A.shape[0]], A.reshape(-1)]).reshape(1, -1)]
 
 
@@ -1334,8 +1435,8 @@ class DifferentialActionModelContactFwdDynamics(DifferentialActionModelFreeFwdDy
         [M  Jc^T ; Jc  0] [a ; -lambda] = [tau(u) - nle ; -a0]
     (Schur complement with JMinvJt + inv_damping I), costs.calc(x, u).
     ``enable_force`` selects the force Jacobians d lambda / d(x, u)
-    (contact-fwddyn.hxx:141-156) that CostModelContactForce / ContactFrictionCone
-    read; without it their residual Jacobians are zero, as in the reference."""
+    (contact-fwddyn.hxx:141-156) that CostModelContactForce / ContactFrictionCone /
+    ContactCoPPosition read; without it their residual Jacobians are zero, as in the reference."""
 
     def __init__(self, state, actuation, contacts, costs, inv_damping=0.0, enable_force=False):
         if not isinstance(actuation, ActuationModelFloatingBase):
@@ -1402,15 +1503,17 @@ class DifferentialActionModelContactFwdDynamics(DifferentialActionModelFreeFwdDy
             if not it.active:
                 continue
             size = int(out[0, o + 3])
-            if it.cost.type in (COST_CONTACT_FORCE, COST_FRICTION_CONE):
+            if it.cost.type in (COST_CONTACT_FORCE, COST_FRICTION_CONE, COST_COP_POSITION):
                 fid = it.cost.frame_id
                 if fid not in rows:
                     raise ValueError(f"Invalid argument: there is not contact defined for frame {fid}")
                 row0, nci = rows[fid]
                 if it.cost.type == COST_CONTACT_FORCE and nci != it.cost.activation.nr:
                     raise ValueError("Invalid argument: the contact-force cost and its contact differ in size")
+                if it.cost.type == COST_COP_POSITION and nci != 6:
+                    raise ValueError("Invalid argument: the CoP position cost needs a ContactModel6D on its frame")
                 out[:, o + COST_HDR] = row0
-                if it.cost.type == COST_FRICTION_CONE:
+                if it.cost.type in (COST_FRICTION_CONE, COST_COP_POSITION):
                     out[:, o + COST_HDR + 1] = nci
             o += size
         return out
@@ -1566,7 +1669,8 @@ class ActionModelImpulseFwdDynamics(_impulse_model_base()):
 
     def pack(self):
         recs = self.impulses.pack()
-        if any(it.active and it.cost.type in (COST_FRAME_VELOCITY, COST_CONTACT_FORCE, COST_FRICTION_CONE)
+        if any(it.active and it.cost.type in (COST_FRAME_VELOCITY, COST_CONTACT_FORCE, COST_FRICTION_CONE,
+                                              COST_COP_POSITION)
                for it in self.costs.costs.values()):
             raise NotImplementedError("crocoddyl_amd: frame-velocity / force costs on impulse knots are not covered")
         if self.impulses.ni > MAX_CONTACT_ROWS:

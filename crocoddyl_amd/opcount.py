@@ -89,8 +89,10 @@ def _cost_terms(dam, n, nu, L, robot, par):
         c = it.cost
         nr = c.activation.nr
         calc += 20 * nr
-        if isinstance(c, (mb.CostModelFramePlacement, mb.CostModelFrameTranslation, mb.CostModelFrameVelocity)):
-            ref = getattr(c, "Mref", None) or getattr(c, "xref", None) or getattr(c, "vref", None)
+        if isinstance(c, (mb.CostModelFramePlacement, mb.CostModelFrameTranslation, mb.CostModelFrameVelocity,
+                          mb.CostModelFrameRotation)):
+            ref = (getattr(c, "Mref", None) or getattr(c, "xref", None) or getattr(c, "vref", None)
+                   or getattr(c, "Rref", None))
             d = _frame_depth(robot, ref.id, par)
             calc += 150
             cols = L if isinstance(c, mb.CostModelFrameVelocity) else n
@@ -104,7 +106,7 @@ def _cost_terms(dam, n, nu, L, robot, par):
         elif isinstance(c, mb.CostModelControl):
             calc += 2 * nu
             diff += 4 * nu
-        else:  # contact force / friction cone: rows of lambda and d lambda / d(x, u)
+        else:  # contact force / friction cone / CoP position: rows of lambda and d lambda / d(x, u)
             cols = L + nu
             diff += nr * cols * (cols + 1) + 2 * nr * cols
     return calc, diff

@@ -36,19 +36,21 @@ CONFIGS = {
 }
 
 
-def gait_models(name, T=None):
+def gait_models(name, T=None, copSupport=None):
     """(gait builder, running models, terminal model) of a gait config. The knot
     counts are the reference benchmark's gait parameters stretched to the config's
     T: Talos walking (benchmark/bipedal_walk_optctrl.py:82-90: step 0.6 m / 0.1 m,
     dt 0.0375, 1 support knot) with 48 step knots -> T = 100; Solo12 trotting
     (benchmark/quadrupedal_gaits_optctrl.py:134-142: step 0.15 m / 0.1 m, dt 1e-2,
     2 support knots) with 27 step knots -> T = 60. A smaller T shortens the steps
-    (for parity tests)."""
+    (for parity tests). ``copSupport`` = (L, W): the biped's feet get a
+    CostModelContactCoPPosition each (gaits.SimpleBipedGaitProblem)."""
     from . import gaits, robots
     kind, _, _, T0, _, dt = CONFIGS[name]
     T = T0 if T is None else T
     if kind == "gait_biped":
-        g = gaits.SimpleBipedGaitProblem(robots.sample_talos(), "right_sole_link", "left_sole_link")
+        g = gaits.SimpleBipedGaitProblem(robots.sample_talos(), "right_sole_link", "left_sole_link",
+                                         copSupport=copSupport)
         sk = max(1, T // 2 - 2)
         models = g.createWalkingModels(g.rmodel.defaultState, 0.6, 0.1, dt, sk, 1)
     else:
@@ -59,12 +61,12 @@ def gait_models(name, T=None):
     return g, models, models[-1]
 
 
-def build_gait(name, T=None, B=None, seed=None, spread=0.02, v_spread=0.1):
+def build_gait(name, T=None, B=None, seed=None, spread=0.02, v_spread=0.1, copSupport=None):
     """(x0s, running, terminal) of a gait config: x0_b = the reference posture
     integrated along a seeded tangent perturbation (q +- spread, v +- v_spread)."""
     _, _, _, T0, B0, _ = CONFIGS[name]
     B = B0 if B is None else B
-    g, running, terminal = gait_models(name, T)
+    g, running, terminal = gait_models(name, T, copSupport)
     rng = np.random.default_rng(seed_of(name) + 1 if seed is None else seed)
     x0 = g.rmodel.defaultState
     nv = g.state.nv
@@ -192,7 +194,7 @@ def build_hetero(name, T=None, B=None, seed=None, phase=10, impulse_every=7):
 
 def build_arm_contact(T=4, B=2, seed=0, robot=None, dt=1e-2, contact="6d", gains=(2.0, 1.5), damping=0.0,
                       weighted=False, armature=None, inactive=False, q_nominal=None, spread=1.0, force_costs=False,
-                      enable_force=None):
+                      enable_force=None, cop=None, cop_weights=None, cop_inactive=False, frot=False):
     """Contact-dynamics knots on the arm: Euler(dt) ∘ DifferentialActionModelContactFwdDynamics
     (contact-fwddyn.hxx) with ActuationModelFloatingBase (first joint unactuated)
     and a ContactModelMultiple on the gripper frame ("6d": ContactModel6D, "3d":
@@ -204,7 +206,11 @@ def build_arm_contact(T=4, B=2, seed=0, robot=None, dt=1e-2, contact="6d", gains
     manifold: the Baumgarte gains pull the frames back); with ``q_nominal``,
     q0_b ~ q_nominal + U[-spread, spread]^nq and v0_b ~ U[-spread, spread]^nv.
     ``force_costs`` adds a CostModelContactForce per contact (a weighted one on the
-    elbow); ``enable_force`` defaults to ``force_costs``."""
+    elbow); ``enable_force`` defaults to ``force_costs`` (or ``cop``). ``cop`` = (L, W)
+    adds a CostModelContactCoPPosition on the gripper's 6D contact (QuadraticBarrier,
+    or WeightedQuadraticBarrier with the four ``cop_weights``; with ``cop_inactive``
+    also on a switched-off 6D contact of the elbow frame); ``frot`` a
+    CostModelFrameRotation on the elbow frame."""
     from . import multibody as mb
     rng = np.random.default_rng(seed)
     model = mb.sample_talos_arm() if robot is None else robot
@@ -244,8 +250,17 @@ def build_arm_contact(T=4, B=2, seed=0, robot=None, dt=1e-2, contact="6d", gains
             costs.addCost("elbowForce", mb.CostModelContactForce(
                 state, mb.ActivationModelWeightedQuad(np.array([1.0, 2.0, 3.0])), mb.FrameForce(eid, np.zeros(6)), nu),
                 1e-2)
-    dam = mb.DifferentialActionModelContactFwdDynamics(state, act, contacts, costs, damping,
-                                                       force_costs if enable_force is None else enable_force)
+    if cop is not None:
+        costs.addCost("gripperCoP", _cop_cost(mb, state, fid, cop, cop_weights, nu), 0.2)
+        if cop_inactive:
+            contacts.addContact("auxCoP", mb.ContactModel6D(state, mb.FramePlacement(eid, mb.SE3.Identity()), nu, gains),
+                                active=False)
+            costs.addCost("auxCoP", _cop_cost(mb, state, eid, cop, cop_weights, nu), 0.2)
+    if frot:
+        costs.addCost("elbowRot", mb.CostModelFrameRotation(state, mb.FrameRotation(eid, _frot_ref(mb)), nu), 0.4)
+    dam = mb.DifferentialActionModelContactFwdDynamics(
+        state, act, contacts, costs, damping,
+        (force_costs or cop is not None) if enable_force is None else enable_force)
     if armature is not None:
         dam.armature = armature
     running = IntegratedActionModelEuler(dam, dt)
@@ -258,10 +273,27 @@ def build_arm_contact(T=4, B=2, seed=0, robot=None, dt=1e-2, contact="6d", gains
     return x0s, [running] * T, terminal
 
 
-def impulse_model(robot=None, kind="6d", r_coeff=0.0, damping=0.0, weighted=False, armature=None, inactive=False):
+def _cop_cost(mb, state, fid, box, weights, nu):
+    """CostModelContactCoPPosition on frame fid with support region ``box`` = (L, W): the
+    default QuadraticBarrier, or a WeightedQuadraticBarrier with ``weights``."""
+    sup = mb.FrameCoPSupport(fid, box)
+    if weights is None:
+        return mb.CostModelContactCoPPosition(state, sup, nu)
+    bounds = mb.ActivationBounds(np.zeros(4), np.full(4, mb.DBL_MAX))
+    return mb.CostModelContactCoPPosition(state, mb.ActivationModelWeightedQuadraticBarrier(bounds, weights), sup, nu)
+
+
+def _frot_ref(mb):
+    """The reference rotation of the synthetic FrameRotation costs."""
+    return mb._rot_axis(np.array([0.6, 0.0, 0.8]), -0.5)
+
+
+def impulse_model(robot=None, kind="6d", r_coeff=0.0, damping=0.0, weighted=False, armature=None, inactive=False,
+                  frot=False):
     """ActionModelImpulseFwdDynamics on the arm's gripper ("6d": ImpulseModel6D,
     "3d": ImpulseModel3D, "6d+3d": plus a 3D impulse on the elbow frame),
-    costs xReg (+ an elbow FrameTranslation when ``weighted``)."""
+    costs xReg (+ an elbow FrameTranslation when ``weighted``, an elbow
+    CostModelFrameRotation with ``frot``)."""
     from . import multibody as mb
     model = mb.sample_talos_arm() if robot is None else robot
     if not model.existFrame("elbow_site"):
@@ -281,6 +313,8 @@ def impulse_model(robot=None, kind="6d", r_coeff=0.0, damping=0.0, weighted=Fals
     if weighted:
         costs.addCost("elbowTrans", mb.CostModelFrameTranslation(state, mb.FrameTranslation(eid, (0.1, 0.0, 0.2)),
                                                                  0), 0.3)
+    if frot:
+        costs.addCost("elbowRot", mb.CostModelFrameRotation(state, mb.FrameRotation(eid, _frot_ref(mb)), 0), 0.4)
     am = mb.ActionModelImpulseFwdDynamics(state, imps, costs, r_coeff, damping)
     if armature is not None:
         am.armature = armature
@@ -304,7 +338,8 @@ def build_arm_impact(T=8, B=2, seed=0, dt=1e-2, r_coeff=0.0):
 ARM_BENT = (0.3, 0.4, -0.2, -1.3, 0.1, 0.6, 0.0)
 
 
-def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, armature=None, w_x=1e-4, w_u=1e-4):
+def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, armature=None, w_x=1e-4, w_u=1e-4,
+              frot=False):
     """The reference's arm-manipulation problem (benchmark/factory/arm.hpp:31-96,
     benchmark/arm-manipulation-optctrl.cpp:20-40) on real multibody knots:
     Euler(dt) ∘ DifferentialActionModelFreeFwdDynamics with costs
@@ -314,7 +349,8 @@ def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, ar
     multibody.RobotModel (default: the 7-DoF Talos-class arm, C3's robot).
     ``weighted`` adds a weighted xReg activation and a FrameTranslation cost
     (parity coverage of the remaining cost / activation kinds). w_x / w_u: the
-    xReg / uReg weights (the factory's 1e-4 by default)."""
+    xReg / uReg weights (the factory's 1e-4 by default). ``frot`` adds a
+    CostModelFrameRotation on the gripper."""
     from . import multibody as mb
     _, _, _, T0, B0, _ = CONFIGS["C3_talos_arm"]
     T = T0 if T is None else T
@@ -335,6 +371,8 @@ def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, ar
     else:
         costs.addCost("xReg", mb.CostModelState(state), w_x)
     costs.addCost("uReg", mb.CostModelControl(state), w_u)
+    if frot:
+        costs.addCost("gripperRot", mb.CostModelFrameRotation(state, mb.FrameRotation(fid, _frot_ref(mb))), 0.4)
     dam = mb.DifferentialActionModelFreeFwdDynamics(state, act, costs)
     if armature is not None:
         dam.armature = armature
@@ -360,7 +398,8 @@ def random_floating_state(model, rng, B, spread=0.3, v_spread=0.5):
 
 def build_floating(T=4, B=2, seed=0, robot=None, dt=1e-2, contacts=(), gains=(2.0, 1.5), damping=0.0,
                    weighted=False, com=False, force_costs=False, enable_force=None, armature=None, spread=0.3,
-                   friction=False, fvel=False, barrier=False):
+                   friction=False, fvel=False, barrier=False, cop=None, cop_weights=None, cop_inactive=False,
+                   frot=False):
     """Floating-base knots (the reference's legged-robot models, on a tree below a
     free-flyer root): Euler(dt) ∘ DifferentialAction{Free,Contact}FwdDynamics with
     ActuationModelFloatingBase (nu = nv - 6). ``contacts``: ("6d" | "3d", frame
@@ -372,7 +411,11 @@ def build_floating(T=4, B=2, seed=0, robot=None, dt=1e-2, contacts=(), gains=(2.
     CostModelContactFrictionCone per contact (QuadraticBarrier on the cone bounds, a
     tilted surface normal); ``fvel``: a CostModelFrameVelocity on the tip;
     ``barrier``: a WeightedQuadraticBarrier state-bounds cost and a QuadraticBarrier
-    control-bounds cost (finite bounds the random states cross)."""
+    control-bounds cost (finite bounds the random states cross). ``cop`` = (L, W): a
+    CostModelContactCoPPosition on every 6D contact (QuadraticBarrier, or
+    WeightedQuadraticBarrier with the four ``cop_weights``; with ``cop_inactive`` also
+    on a switched-off 6D contact of the mid_site frame); ``frot``: a
+    CostModelFrameRotation on the mid_site frame."""
     from . import multibody as mb
     rng = np.random.default_rng(seed)
     model = mb.sample_tree(5, seed=3, freeflyer=True) if robot is None else robot
@@ -406,6 +449,9 @@ def build_floating(T=4, B=2, seed=0, robot=None, dt=1e-2, contacts=(), gains=(2.
             bounds, np.linspace(1.0, 3.0, nd)), state.zero(), nu), 5.0)
         costs.addCost("uBounds", mb.CostModelControl(state, mb.ActivationModelQuadraticBarrier(
             mb.ActivationBounds(np.full(nu, -0.5), np.full(nu, 0.5))), nu), 3.0)
+    if frot:
+        costs.addCost("midRot", mb.CostModelFrameRotation(state, mb.FrameRotation(
+            model.getFrameId("mid_site"), _frot_ref(mb)), nu), 0.4)
     if contacts:
         cm = mb.ContactModelMultiple(state, nu)
         for i, (kind, fname) in enumerate(contacts):
@@ -424,7 +470,14 @@ def build_floating(T=4, B=2, seed=0, robot=None, dt=1e-2, contacts=(), gains=(2.
                 costs.addCost(f"cone{i}", mb.CostModelContactFrictionCone(
                     state, mb.ActivationModelQuadraticBarrier(mb.ActivationBounds(cone.lb, cone.ub)),
                     mb.FrameFrictionCone(fid, cone), nu), 0.1)
-        ef = (force_costs or friction) if enable_force is None else enable_force
+            if cop is not None and kind == "6d":
+                costs.addCost(f"cop{i}", _cop_cost(mb, state, fid, cop, cop_weights, nu), 0.2)
+        if cop is not None and cop_inactive:
+            mid = model.getFrameId("mid_site")
+            cm.addContact("off_mid", mb.ContactModel6D(state, mb.FramePlacement(mid, mb.SE3.Identity()), nu, gains),
+                          active=False)
+            costs.addCost("copOff", _cop_cost(mb, state, mid, cop, cop_weights, nu), 0.2)
+        ef = (force_costs or friction or cop is not None) if enable_force is None else enable_force
         dam = mb.DifferentialActionModelContactFwdDynamics(state, act, cm, costs, damping, ef)
     else:
         dam = mb.DifferentialActionModelFreeFwdDynamics(state, act, costs)

@@ -15,10 +15,11 @@
 //   ActivationModelQuad / WeightedQuad / QuadraticBarrier / WeightedQuadraticBarrier,
 //     ActivationBounds                        core/activations/*.hpp
 //   FrictionCone                              multibody/friction-cone.hxx:24-96
-//   FramePlacement / FrameTranslation / FrameMotion / FrameForce / FrameFrictionCone
-//                                             multibody/frames.hpp
-//   CostModelState / Control / FramePlacement / FrameTranslation / FrameVelocity /
-//     CoMPosition / ContactForce / ContactFrictionCone, CostModelSum
+//   FramePlacement / FrameTranslation / FrameRotation / FrameMotion / FrameForce /
+//     FrameFrictionCone / FrameCoPSupport     multibody/frames.hpp
+//   CostModelState / Control / FramePlacement / FrameTranslation / FrameRotation /
+//     FrameVelocity / CoMPosition / ContactForce / ContactFrictionCone /
+//     ContactCoPPosition, CostModelSum
 //                                             multibody/costs/*.hxx, cost-sum.hxx:18-160
 //   ContactModel3D / ContactModel6D, ContactModelMultiple   multibody/contacts/*.hxx
 //   DifferentialActionModelFreeFwdDynamics    multibody/actions/free-fwddyn.hxx:24-160
@@ -47,7 +48,7 @@ enum { kJointRec = 27, kCostHdr = 4, kMaxContactRows = 24, kMaxDofs = 64 };
 enum { JOINT_REVOLUTE = 0, JOINT_FREEFLYER = 1 };
 enum { COST_STATE = 1, COST_CONTROL = 2, COST_FRAME_PLACEMENT = 3, COST_FRAME_TRANSLATION = 4, CONTACT_3D = 5,
        CONTACT_6D = 6, COST_CONTACT_FORCE = 7, COST_COM_POSITION = 8, COST_FRICTION_CONE = 9,
-       COST_FRAME_VELOCITY = 10 };
+       COST_FRAME_VELOCITY = 10, COST_COP_POSITION = 11, COST_FRAME_ROTATION = 12 };
 enum { ACT_QUAD = 0, ACT_WEIGHTED_QUAD = 1, ACT_QUAD_BARRIER = 2, ACT_WEIGHTED_QUAD_BARRIER = 3 };
 static const double kInactiveForceRow = -2.;  // the contact exists but is inactive
 
@@ -612,6 +613,32 @@ struct FrameFrictionCone {
   FrictionCone cone;
   FrameFrictionCone(int i, const FrictionCone& c) : id(i), cone(c) {}
 };
+struct FrameRotation {
+  int id;
+  Mat3 rotation;
+  FrameRotation(int i, const Mat3& R) : id(i), rotation(R) {}
+};
+// FrameCoPSupport(id, support_region) (the reference fork's frames.hpp): the foot's extent
+// (L, W) along the contact frame's x and y, centred on the frame origin; A (4 x 6) on the
+// wrench (fx, fy, fz, tx, ty, tz): A f >= 0 keeps the centre of pressure (-ty / fz, tx / fz)
+// inside the region for fz > 0
+struct FrameCoPSupport {
+  int id;
+  double support_region[2];
+  double A[4][6];
+  FrameCoPSupport(int i, double L, double W) : id(i) { update_A(L, W); }
+  void update_A(double L, double W) {
+    if (!(L > 0.) || !(W > 0.)) throw Exception("Invalid argument: the support region's extents have to be positive");
+    support_region[0] = L;
+    support_region[1] = W;
+    const double a[4][6] = {{0., 0., L / 2, 0., -1., 0.},
+                            {0., 0., L / 2, 0., 1., 0.},
+                            {0., 0., W / 2, 1., 0., 0.},
+                            {0., 0., W / 2, -1., 0., 0.}};
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 6; ++c) A[r][c] = a[r][c];
+  }
+};
 
 // ---- costs (multibody/costs/*.hxx) -----------------------------------------
 // A record: [type, weight (set by the sum), activation kind, size] + payload +
@@ -714,6 +741,25 @@ class CostModelFrameTranslation : public CostModelAbstract {
   FrameTranslation xref_;
 };
 
+// r = log3(Rref^T oRf) (frame-rotation.hxx); parity unpinned against the reference binary
+class CostModelFrameRotation : public CostModelAbstract {
+ public:
+  CostModelFrameRotation(std::shared_ptr<StateMultibody> s, std::shared_ptr<ActivationModelAbstract> a,
+                         const FrameRotation& Rref, int nu)
+      : CostModelAbstract(s, a, 3, nu), Rref_(Rref) {}
+  CostModelFrameRotation(std::shared_ptr<StateMultibody> s, const FrameRotation& Rref, int nu)
+      : CostModelFrameRotation(s, nullptr, Rref, nu) {}
+  int type() const { return COST_FRAME_ROTATION; }
+
+ protected:
+  void payload(VectorXd& out) const {  // Rref^T in the order the placement record keeps Mref^-1's rotation
+    state_->get_pinocchio()->pack_frame(Rref_.id, out);
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) out.push_back(Rref_.rotation(i, j));
+  }
+  FrameRotation Rref_;
+};
+
 // r = v_f - vref, LOCAL (frame-velocity.hxx:53-84)
 class CostModelFrameVelocity : public CostModelAbstract {
  public:
@@ -794,6 +840,33 @@ class CostModelContactFrictionCone : public CostModelAbstract {
       for (int c = 0; c < 3; ++c) out.push_back(r[c]);
   }
   FrameFrictionCone fref_;
+};
+
+// r = A lambda of the ContactModel6D on cop_support.id (the reference fork's
+// contact-cop-position.hpp); QuadraticBarrier(0, DBL_MAX) by default. Parity unpinned
+// against the reference binary.
+class CostModelContactCoPPosition : public CostModelAbstract {
+ public:
+  CostModelContactCoPPosition(std::shared_ptr<StateMultibody> s, std::shared_ptr<ActivationModelAbstract> a,
+                              const FrameCoPSupport& cop_support, int nu)
+      : CostModelAbstract(s, a ? a : default_activation(), 4, nu), cop_support_(cop_support) {}
+  CostModelContactCoPPosition(std::shared_ptr<StateMultibody> s, const FrameCoPSupport& cop_support, int nu)
+      : CostModelContactCoPPosition(s, nullptr, cop_support, nu) {}
+  int type() const { return COST_COP_POSITION; }
+  int contact_frame() const { return cop_support_.id; }
+
+ protected:
+  static std::shared_ptr<ActivationModelAbstract> default_activation() {
+    return std::make_shared<ActivationModelQuadraticBarrier>(ActivationBounds(VectorXd(4, 0.), VectorXd(4, DBL_MAX)));
+  }
+  void payload(VectorXd& out) const {  // [row0 (the DAM's), contact rows (the DAM's), nr, A row-major]
+    out.push_back(-1.);
+    out.push_back(0.);
+    out.push_back(4.);
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 6; ++c) out.push_back(cop_support_.A[r][c]);
+  }
+  FrameCoPSupport cop_support_;
 };
 
 // CostModelSum (cost-sum.hxx:18-85): named costs in a std::map (evaluated in name order)
@@ -1019,13 +1092,15 @@ class DifferentialActionModelContactFwdDynamics : public DifferentialActionModel
       if (!kv.second.active) continue;
       const size_t size = (size_t)out[c + 3];
       const int ty = kv.second.cost->type();
-      if (ty == COST_CONTACT_FORCE || ty == COST_FRICTION_CONE) {
+      if (ty == COST_CONTACT_FORCE || ty == COST_FRICTION_CONE || ty == COST_COP_POSITION) {
         auto it = rows.find(kv.second.cost->contact_frame());
         if (it == rows.end()) throw Exception("Invalid argument: there is not contact defined for a force cost's frame");
         if (ty == COST_CONTACT_FORCE && it->second.second != kv.second.cost->get_activation()->get_nr())
           throw Exception("Invalid argument: the contact-force cost and its contact differ in size");
+        if (ty == COST_COP_POSITION && it->second.second != 6)
+          throw Exception("Invalid argument: the CoP position cost needs a ContactModel6D on its frame");
         out[c + kCostHdr] = it->second.first;
-        if (ty == COST_FRICTION_CONE) out[c + kCostHdr + 1] = it->second.second;
+        if (ty == COST_FRICTION_CONE || ty == COST_COP_POSITION) out[c + kCostHdr + 1] = it->second.second;
       }
       c += size;
     }
@@ -1120,7 +1195,8 @@ class ActionModelImpulseFwdDynamics : public ActionModelBase {
   void pack(VectorXd& out) const {
     for (const auto& kv : costs_->get_costs()) {
       const int ty = kv.second.cost->type();
-      if (kv.second.active && (ty == COST_FRAME_VELOCITY || ty == COST_CONTACT_FORCE || ty == COST_FRICTION_CONE))
+      if (kv.second.active && (ty == COST_FRAME_VELOCITY || ty == COST_CONTACT_FORCE || ty == COST_FRICTION_CONE ||
+                               ty == COST_COP_POSITION))
         throw Exception("crocoddyl_amd: frame-velocity / force costs on impulse knots are not covered");
     }
     if (impulses_->get_ni() > kMaxContactRows) throw Exception("Invalid argument: the device path holds at most 24 impulse rows");

@@ -105,6 +105,13 @@ int fddp_abi_version(void);
  *       knots only): [row0, contact rows, nr, A(nr x 3, row-major)]: r = A lambda_lin
  *    10 CostModelFrameVelocity (frame-velocity.hxx:53-84, Euler knots): frame
  *       joint, frame placement R(9) p(3), vref(6) (LOCAL); nr = 6
+ *    11 CostModelContactCoPPosition (contact-cop-position.hpp of the reference
+ *       fork, contact knots only): [row0, contact rows (6), nr, A(nr x 6,
+ *       row-major)]: r = A lambda of a 6D contact's six multipliers, row0 as for 7;
+ *       nr in [1, 6] (the support region's A has 4 rows)
+ *    12 CostModelFrameRotation (frame-rotation.hxx): frame joint, frame
+ *       placement R(9) p(3), Rref^T (9, in the order of 3's Mref^-1 R);
+ *       r = log3(Rref^T oRf), nr = 3
  * At most 64 dofs, 64 cost records and 64 stacked residual rows with dense
  * Jacobians per knot (the calcDiff LDS plan must fit; fddp_create says why not). */
 #define FDDP_KNOT_EULER_FREEFWD 4
@@ -116,7 +123,7 @@ int fddp_abi_version(void);
  * Baumgarte gains). Block: the FDDP_KNOT_EULER_FREEFWD layout (header size covers
  * everything; dt = 0 is the biped's pseudo-impulse knot), then
  *   [nun, JMinvJt_damping, ncontact, flag (0; 2 = enable_force: the force
- *    Jacobians the contact-force / friction-cone costs read)]
+ *    Jacobians the contact-force / friction-cone / CoP-position costs read)]
  *   ncontact active contact records in name order, each
  *     [type (5: 3D, 6: 6D), gains[0], gains[1], size], frame joint, frame
  *     placement in that joint R(9) p(3), then 3D: reference translation(3);
