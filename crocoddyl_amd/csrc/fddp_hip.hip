@@ -713,6 +713,10 @@ int apply_knots(fddp_handle* h, const fddp_knot_desc* knots, const double* param
     for (int nw : {1, 4, 8})
       F.bwd_code[plan::bwd_slot(nw)] = ktab::backward_mfma_setup(L.ntl, L.mtl, nw, d.ndx, &F.bwd_occ[plan::bwd_slot(nw)]);
   P.var = plan::plan_variants(L, d, P.ov, F);
+  // the three-waves-per-EU rollout object has no code for the impulse CoM cost
+  // (MB_CALC_IMPULSE_COM): a plan that pairs them is an error here, never a missing cost there
+  if (L.has_icom && P.var.fwd == ktab::FWD_MB)
+    return fail(FDDP_ERR_UNSUPPORTED, "the rollout variant chosen does not evaluate the impulse CoM cost");
   if (L.npar_adapt && !L.fast && std::getenv("FDDP_STAMPS"))  // (diagnostic runs: the rollout's residency)
     std::fprintf(stderr, "[fddp] rollout: %.0f workgroups on %d CUs (LDS %zu B per workgroup)\n", P.var.ls_slots, F.cus,
                  L.fwd_smem);

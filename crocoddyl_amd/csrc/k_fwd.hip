@@ -15,6 +15,11 @@
 #define MB_BLK_UNIFORM 1
 #define MB_LANE_OPAQUE 1
 #endif
+// the three-waves-per-EU variant never runs a horizon with a CostModelImpulseCoM record
+// (launch_plan.hpp plan_variants), so its calc is built without that cost's phases
+#if defined(FDDP_TU_FWD) && FDDP_TU_FWD == 1
+#define MB_CALC_IMPULSE_COM 0
+#endif
 #include "fast_path.hpp"
 #include "fddp_kernels.hpp"
 #include "ktab.hpp"

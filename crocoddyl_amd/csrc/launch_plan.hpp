@@ -58,6 +58,7 @@ struct LdsPlan {
   const char* error = nullptr;  // a refusal (FDDP_ERR_INVALID_ARG): the plan is not usable
   bool has_mb = false;          // multibody knots present (mb_knot_kernel)
   bool all_mb = false;          // every knot is a multibody knot
+  bool has_icom = false;        // a knot carries a CostModelImpulseCoM record (no FWD_MB rollout)
   int mb_nj = 0;                // largest multibody tree (dofs)
   int64_t mbw = 0, mbw_fwd = 0, mbd = 0;  // Dev::mbw, mbw_fwd, mbd
   int mbspill = 0, dxv_mbw = 0;           // Dev::mbspill, dxv_mbw
@@ -171,10 +172,14 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
       want = kCHdr + 19 + ap * 6;
     }
     if (type == C_COM_POSITION) want = kCHdr + 3 + ap * 3;
+    if (type == C_IMPULSE_COM) {  // empty payload: the activation parameters follow the header
+      if (!impulse) return why = "the impulse CoM cost needs an impulse knot", -1;
+      want = kCHdr + ap * 3;
+    }
     if (type == C_CONTACT_FORCE || type == C_FRICTION_CONE || type == C_COP_POSITION) {
       // [row0, nr, fref(6)] | [row0, nc, nr, A(3 nr)] | [row0, nc, nr, A(6 nr)]; rows checked against the
-      // contacts below
-      if (kind != FDDP_KNOT_EULER_CONTACTFWD) return why = "force costs need contact knots", -1;
+      // contacts below (on an impulse knot: against its impulses, whose multipliers the rows index)
+      if (!contact && !impulse) return why = "force costs need contact knots", -1;
       if (o + kCHdr + 3 > size) return why = "cost records out of range", -1;
       const int row0 = (int)C[kCHdr];
       if ((double)row0 != C[kCHdr] || (row0 < 0 && row0 != kInactiveForceRow))
@@ -187,7 +192,8 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
       } else if (type == C_COP_POSITION) {
         const int ncc = (int)C[kCHdr + 1], nrc = (int)C[kCHdr + 2];
         if ((double)nrc != C[kCHdr + 2] || nrc < 1 || nrc > 6) return why = "CoP support rows out of [1, 6]", -1;
-        if (row0 >= 0 && ncc != 6) return why = "CoP position cost on a contact of 6 rows", -1;
+        if (row0 >= 0 && ncc != 6)
+          return why = impulse ? "CoP position cost on an impulse of 6 rows" : "CoP position cost on a contact of 6 rows", -1;
         want = kCHdr + 3 + 6 * nrc + ap * nrc;
         if (row0 >= 0) force_rows = std::max(force_rows, row0 + ncc);
       } else {
@@ -209,18 +215,18 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
       for (int e = 0; e < 7; ++e)
         if (!std::isfinite(C[kCHdr + e])) return why = "non-finite reference state", -1;
     if (type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_COM_POSITION ||
-        type == C_FRAME_VELOCITY || type == C_FRAME_ROTATION || (type == C_STATE && ff))
+        type == C_FRAME_VELOCITY || type == C_FRAME_ROTATION || type == C_IMPULSE_COM || (type == C_STATE && ff))
       ++njac;
     if (type == C_FRAME_VELOCITY) vcols = true;
     o += rs;
   }
   int nc = 0;
   std::vector<std::pair<int, int>> crow;  // (row0, rows) of every contact record
-  if (contact || impulse) {  // [nun | r_coeff, damping, ncontact, 0 | 1 | 2] + contact / impulse records
+  if (contact || impulse) {  // [nun | r_coeff, damping, ncontact, 0 | 2 (contact), 1 | 3 (impulse)] + records
     if (o + 4 > size) return why = "contact section out of range", -1;
     const int nun = (int)P[o], ncon = (int)P[o + 2];
     const double damping = P[o + 1];
-    if (impulse ? P[o + 3] != 1. : (P[o + 3] != 0. && P[o + 3] != 2.))
+    if (impulse ? (P[o + 3] != 1. && P[o + 3] != 3.) : (P[o + 3] != 0. && P[o + 3] != 2.))
       return why = "contact / impulse section flag does not match the kind", -1;
     if (impulse) {
       if (!(P[o] >= 0.) || !std::isfinite(P[o])) return why = "The restitution coefficient has to be positive", -1;
@@ -252,7 +258,8 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
     }
     if (nc > kMaxNc) return why = "more than 24 contact rows in one knot", -1;
   }
-  if (force_rows > nc) return why = "contact-force cost reads rows beyond the contacts", -1;
+  if (force_rows > nc)
+    return why = impulse ? "impulse cost reads rows beyond the impulses" : "contact-force cost reads rows beyond the contacts", -1;
   if (force_rows > 0) {  // each contact-force cost reads exactly one contact of its size
     int64_t oc = FDDP_PARAM_HEADER + 3 + nj + (int64_t)kJRec * nb;
     for (int k = 0; k < ncost; ++k) {
@@ -319,6 +326,7 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
         const int64_t s1 = mb_block_check(params + off, n_params - off, knots[t].kind, d.nx, knots[t].nu, why, &k.nj,
                                           &k.njac, &k.nc, &k.vcols, &k.nu, &k.nrows);
         if (s1 < 0 && !refused) refused = why.text;
+        if (s1 >= 0 && fddp::mb::has_impulse_com(fddp::mb::parse(params + off))) p.has_icom = true;
         // (a refused block is planned with its size field, as mb_pmax is: the budget below
         // then refuses only what is over it)
         const int64_t own = (int64_t)params[off + 3];
@@ -400,6 +408,8 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
   p.ntl = (d.ndx + 15) / 16;
   p.mtl = (d.nu_max + 15) / 16;
   if (refused) p.error = refused;
+  if (!p.error && p.has_icom && ov.fwd_mbw == 3)
+    p.error = "FDDP_FWD_MBW=3 on a horizon with an impulse CoM cost: that rollout build does not evaluate it";
   return p;
 }
 
@@ -439,7 +449,9 @@ inline VariantPlan plan_variants(const LdsPlan& l, const fddp_dims& d, const Ove
     v.fwd = ktab::FWD_GENERIC;
   } else {
     const bool three = resident_per_cu(f.fwd_api[ktab::FWD_MB], l.fwd_smem, f.fwd_static[ktab::FWD_MB]) >= 3;
-    const bool take3 = ov.fwd_mbw ? ov.fwd_mbw == 3 : (three && d.B > 2 * cus);
+    // (a horizon with an impulse CoM cost never: that build's calc has no code for it,
+    // MB_CALC_IMPULSE_COM; plan_lds refuses the override that would force it)
+    const bool take3 = !l.has_icom && (ov.fwd_mbw ? ov.fwd_mbw == 3 : (three && d.B > 2 * cus));
     v.fwd = take3 ? ktab::FWD_MB : ktab::FWD_MB2;
   }
   if (!l.fast) v.ls_slots = (double)cus * resident_per_cu(f.fwd_api[v.fwd], l.fwd_smem, f.fwd_static[v.fwd]);

@@ -95,6 +95,13 @@ MB_HD __forceinline__ T* mb_lds(T* p) {
 #ifndef MB_LANE_OPAQUE
 #define MB_LANE_OPAQUE 0
 #endif
+// MB_CALC_IMPULSE_COM (per kernel object): the rollout's calc evaluates CostModelImpulseCoM
+// records (two phases after v+). The three-waves-per-EU rollout object is built without them,
+// at its register cap they cost it spills on every horizon; the launch plan never gives it a
+// horizon with such a record (LdsPlan::has_icom, plan_variants).
+#ifndef MB_CALC_IMPULSE_COM
+#define MB_CALC_IMPULSE_COM 1
+#endif
 
 namespace fddp {
 namespace mb {
@@ -103,7 +110,7 @@ typedef unsigned long long Mask;  // one bit per dof
 constexpr int kMaxJ = 64;         // dofs (nv)
 constexpr int kJRec = 27;         // doubles per joint record
 constexpr int kCHdr = 4;          // doubles of a cost record's header
-constexpr int kMaxJacCosts = 8;   // costs with a dense residual Jacobian (frame, CoM, free-flyer state)
+constexpr int kMaxJacCosts = 8;   // costs with a dense residual Jacobian (frame, CoM, impulse CoM, free-flyer state)
 constexpr int kMaxNc = 24;        // stacked contact rows (FDDP_KNOT_EULER_CONTACTFWD)
 constexpr int kMbDiffNT = 256;    // threads of the knot-parallel calcDiff workgroup
 enum { J_REVOLUTE = 0, J_FREEFLYER = 1 };
@@ -116,6 +123,8 @@ enum {
   C_FRAME_TRANSLATION = 4,
   C_CONTACT_3D = 5,
   C_CONTACT_6D = 6,
+  // (the force costs 7, 9, 11 on an impulse knot read the impulse's multipliers Lambda instead:
+  // CostModelContactImpulse, CostModelImpulseFrictionCone, CostModelImpulseCoPPosition)
   C_CONTACT_FORCE = 7,  // cost on a contact's force: payload [row0, nr, fref(6)] (contact-force.hxx)
   C_COM_POSITION = 8,   // r = com(q) - cref: payload [cref(3)] (com-position.hxx:49-75)
   C_FRICTION_CONE = 9,  // r = A lambda_lin: payload [row0, nc, nr, A (nr x 3 row-major)]
@@ -123,11 +132,12 @@ enum {
   C_FRAME_VELOCITY = 10,  // r = LOCAL frame velocity - vref: frame payload + vref(6) (frame-velocity.hxx:53-84)
   C_COP_POSITION = 11,    // r = A lambda of a 6D contact: payload [row0, nc, nr, A (nr x 6 row-major)]
                           // (contact-cop-position.hpp)
-  C_FRAME_ROTATION = 12   // r = log3(Rref^T oRf): frame payload + Rref^T (9) (frame-rotation.hxx)
+  C_FRAME_ROTATION = 12,  // r = log3(Rref^T oRf): frame payload + Rref^T (9) (frame-rotation.hxx)
+  C_IMPULSE_COM = 13      // r = Jcom(q) (v+ - v) on an impulse knot: empty payload (CostModelImpulseCoM)
 };
 // Activation of a cost record: header slot 2 (core/activations/*.hpp)
 enum { A_QUAD = 0, A_WEIGHTED_QUAD = 1, A_QUAD_BARRIER = 2, A_WEIGHTED_QUAD_BARRIER = 3 };
-constexpr int kInactiveForceRow = -2;  // contact-force cost on an inactive contact: lambda = 0, no Jacobians
+constexpr int kInactiveForceRow = -2;  // force cost on an inactive contact / impulse: lambda = 0, no Jacobians
 
 struct Blk {
   double dt;
@@ -148,7 +158,7 @@ struct Blk {
   // impulse section instead (ActionModelImpulseFwdDynamics, nu = 0)
   bool impulse;
   double r_coeff;     // restitution coefficient
-  bool enable_force;  // contact section flag 2: force Jacobians for CostModelContactForce
+  bool enable_force;  // section flag bit 2 (contact: 2, impulse: 3): the multiplier Jacobians of the force costs
 };
 
 MB_HD inline Blk parse(const double* P) {
@@ -172,9 +182,9 @@ MB_HD inline Blk parse(const double* P) {
   b.impulse = false;
   b.enable_force = false;
   b.r_coeff = 0.;
-  if (e - P < (int64_t)P[3]) {  // [nun | r_coeff, damping, ncontact, 0 | 1 | 2] + records
-    b.impulse = (int)e[3] == 1;
-    b.enable_force = (int)e[3] == 2;
+  if (e - P < (int64_t)P[3]) {  // [nun | r_coeff, damping, ncontact, 0 | 1 | 2 | 3] + records
+    b.impulse = ((int)e[3] & 1) != 0;
+    b.enable_force = ((int)e[3] & 2) != 0;
     b.nun = b.impulse ? b.nj : (int)e[0];
     b.r_coeff = b.impulse ? e[0] : 0.;
     b.damping = e[1];

@@ -134,14 +134,17 @@ MB_HD inline Act cost_act(const Blk& b, const CRec& C, int nu) {
 }
 // costs whose residual Jacobian is dense over the configuration tangent (stored
 // per cost: rows x jw, jw = nj, or 2 nj when a frame-velocity cost needs the
-// velocity columns too): frame costs, CoM, frame velocity, and the free-flyer
-// block of a state cost
+// velocity columns too): frame costs, CoM, frame velocity, the free-flyer block of a
+// state cost, and the impulse CoM cost (its slot holds d(Jcom w)/dq and Jcom, three rows each:
+// the rows of R are formed from them and Fx, knot_calc_diff_x)
 MB_HD __forceinline__ bool jac_cost(const Blk& b, int type) {
   return type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_COM_POSITION ||
-         type == C_FRAME_VELOCITY || type == C_FRAME_ROTATION || (type == C_STATE && b.ff);
+         type == C_FRAME_VELOCITY || type == C_FRAME_ROTATION || type == C_IMPULSE_COM || (type == C_STATE && b.ff);
 }
 MB_HD __forceinline__ int jac_rows(int type) {
-  return (type == C_FRAME_TRANSLATION || type == C_COM_POSITION || type == C_FRAME_ROTATION) ? 3 : 6;
+  const bool three =
+      type == C_FRAME_TRANSLATION || type == C_COM_POSITION || type == C_FRAME_ROTATION || type == C_IMPULSE_COM;
+  return three ? 3 : 6;
 }
 MB_HD inline int count_jac_costs(const Blk& b, bool* vel_cols = nullptr) {
   int n = 0;
@@ -164,11 +167,11 @@ MB_HD __forceinline__ bool force_cost(int type) {
 // columns of the matrix A of a cone / CoP record: the multipliers its rows read (the
 // linear three of the contact, or the whole wrench of a 6D one)
 MB_HD __forceinline__ int force_cols(int type) { return type == C_COP_POSITION ? 6 : 3; }
-// Residual rows with a dense Jacobian (jac costs; force costs on an active contact
-// when the force Jacobians are computed): the rows of the stacked R of calcDiff.
+// Residual rows with a dense Jacobian (jac costs; force costs on an active contact or
+// impulse when the multiplier Jacobians are computed): the rows of the stacked R of calcDiff.
 MB_HD inline int count_cost_rows(const Blk& b, int nu) {
   int n = 0;
-  const bool fd = b.enable_force && b.nc > 0 && !b.impulse;
+  const bool fd = b.enable_force && b.nc > 0;
   const double* cr = b.C;
   for (int k = 0; k < b.ncost; ++k) {
     const CRec C{cr};
@@ -259,6 +262,94 @@ MB_HD inline void com_value(const Blk& b, const WVals& W, double* c) {
   for (int e = 0; e < 3; ++e) c[e] = h[e] / m;
 }
 
+// ---- CostModelImpulseCoM: r = Jcom(q) (v+ - v), the change of the CoM velocity ----------
+// lane i < nj: the mass of dof i's body times the velocity of its CoM under the generalised
+// velocity w (wq(k): its entry k), o[0..2]; from the L records (oMi, S) and the block alone,
+// so the rollout's calc can run it after its factorisation has overwritten the D records.
+template <class Wq>
+MB_HD inline void impulse_com_body(const Blk& b, const WVals& W, Wq wq, int i, double* o) {
+  double v0 = 0., v1 = 0., v2 = 0., v3 = 0., v4 = 0., v5 = 0.;
+  const Mask am = *W.anc(i);
+  for (int k = 0; k < b.nj; ++k) {  // (selected, not branched: as w_velocity)
+    const double wk = ((am >> k) & 1ull) ? wq(k) : 0.;
+    const double* S = W.S(k);
+    v0 += S[0] * wk;
+    v1 += S[1] * wk;
+    v2 += S[2] * wk;
+    v3 += S[3] * wk;
+    v4 += S[4] * wk;
+    v5 += S[5] * wk;
+  }
+  const JRec J(b, rec_of(b, i));
+  const double* R = W.oR(i);  // (column-major, as matvec3 reads it)
+  const double* cl = J.com();
+  const double c0 = W.op(i)[0] + (R[0] * cl[0] + R[3] * cl[1] + R[6] * cl[2]);
+  const double c1 = W.op(i)[1] + (R[1] * cl[0] + R[4] * cl[1] + R[7] * cl[2]);
+  const double c2 = W.op(i)[2] + (R[2] * cl[0] + R[5] * cl[1] + R[8] * cl[2]);
+  const double m = carries_body(b, i) ? J.mass() : 0.;
+  o[0] = m * (v0 + (v4 * c2 - v5 * c1));
+  o[1] = m * (v1 + (v5 * c0 - v3 * c2));
+  o[2] = m * (v2 + (v3 * c1 - v4 * c0));
+}
+// one lane: the residual from the bodies' terms p[stride * i + e] (impulse_com_body), summed in
+// dof order and divided by the total mass
+MB_HD inline void impulse_com_sum(const Blk& b, const double* p, int stride, double* r) {
+  double mt = 0., h[3] = {0., 0., 0.};
+  for (int i = 0; i < b.nj; ++i) {
+    if (!carries_body(b, i)) continue;
+    mt += JRec(b, rec_of(b, i)).mass();
+    for (int e = 0; e < 3; ++e) h[e] += p[(int64_t)stride * i + e];
+  }
+  for (int e = 0; e < 3; ++e) r[e] = h[e] / mt;
+}
+// whether the block has an impulse CoM cost (impulse knots only: the plan refuses it elsewhere)
+MB_HD inline bool has_impulse_com(const Blk& b) {
+  if (!b.impulse) return false;
+  bool found = false;
+  const double* cr = b.C;
+  for (int k = 0; k < b.ncost; ++k) {
+    const CRec C{cr};
+    found = found || C.type() == C_IMPULSE_COM;
+    cr += C.size();
+  }
+#if MB_BLK_UNIFORM && defined(__HIP_DEVICE_COMPILE__)
+  found = mb_uniform(found);  // the same in every lane: the phases it selects end in barriers
+#endif
+  return found;
+}
+// (out of line on the device: inlined they changed the inlining of the rollout kernel around
+// them, and its split gains loop's arrays went to scratch)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MB_NOINLINE_DEV __attribute__((noinline))
+#else
+#define MB_NOINLINE_DEV inline
+#endif
+// The rollout's calc, after v+ (vp; nc == 0: v+ = v): two phases on every lane of the
+// workgroup. First the bodies' terms into the velocity slots of the L records (unused on an
+// impulse knot's calc), then record k's weighted value on lane 64 + k into cv[k].
+MB_HD MB_NOINLINE_DEV void impulse_com_calc_bodies(const Blk& b, const WVals& W, const double* x, const double* vp, int lane) {
+  if (lane >= b.nj) return;
+  const double* v = x + b.nq;
+  const bool act = b.nc > 0;
+  double o[3];
+  impulse_com_body(b, W, [=](int k) { return act ? vp[k] - v[k] : 0.; }, lane, o);
+  for (int e = 0; e < 3; ++e) W.v(lane)[e] = o[e];
+}
+MB_HD MB_NOINLINE_DEV void impulse_com_calc_value(const Blk& b, const WVals& W, double* cv, int lane) {
+  const int kf = lane - 64;
+  if (kf < 0 || kf >= b.ncost) return;
+  const double* cr = b.C;
+  for (int k = 0; k < kf; ++k) cr += CRec{cr}.size();
+  const CRec C{cr};
+  if (C.type() != C_IMPULSE_COM) return;
+  double r[3];
+  impulse_com_sum(b, W.v(0), kWRec, r);
+  const Act act = cost_act(b, C, 0);
+  double a = 0.;
+  for (int e = 0; e < 3; ++e) a += act.value2(e, r[e]);
+  cv[kf] = C.weight() * (0.5 * a);
+}
+
 // free-flyer block of a state residual: log6(Mref^-1 M) (multibody.hxx:69)
 MB_HD inline void ff_rel(const double* xref, const double* x, double* Rr, double* pr) {
   double R0[9], R1[9], dp[3];
@@ -287,8 +378,8 @@ MB_HD inline void frame_velocity_res(const Blk& b, const WVals& V, const double*
 }
 
 // Activation value of one cost record (kinematics in V; velocities in V only with
-// vel: frame-velocity costs are skipped without). Force costs return 0: they need
-// the multipliers and are added after the contact solve.
+// vel: frame-velocity costs are skipped without). Force costs and the impulse CoM cost
+// return 0: they need the multipliers / v+ and are added after the contact solve.
 MB_HD __forceinline__ double cost_activation(const Blk& b, const WVals& V, const CRec& C, const double* x,
                                              const double* u, int nu, bool vel = true) {
   const Act act = cost_act(b, C, nu);
@@ -306,7 +397,7 @@ MB_HD __forceinline__ double cost_activation(const Blk& b, const WVals& V, const
     for (int i = i0; i < ndx; ++i) a += act.value2(i, state_res(b, C.d(), x, i));
   } else if (C.type() == C_CONTROL) {
     for (int i = 0; i < nu; ++i) a += act.value2(i, u[i] - C.d()[i]);
-  } else if (force_cost(C.type())) {
+  } else if (force_cost(C.type()) || C.type() == C_IMPULSE_COM) {  // (the impulse CoM cost: after v+)
     return 0.;
   } else if (C.type() == C_COM_POSITION) {
     double c[3];

@@ -834,7 +834,7 @@ MB_HD __forceinline__ double knot_calc_x(const X& ex, const double* P, int nx, c
       // contact-force costs (lambda = -S^-1 r, in S's last column, negated): record k's
       // value on lane 64 + k into cv[k], summed in record order with the next phase
       const int kf = lane - 64;
-      if (kf >= 0 && kf < b.ncost && !imp) {
+      if (kf >= 0 && kf < b.ncost) {
         const double* cr = b.C;
         for (int k = 0; k < kf; ++k) cr += CRec{cr}.size();
         const CRec C{cr};
@@ -850,6 +850,12 @@ MB_HD __forceinline__ double knot_calc_x(const X& ex, const double* P, int nx, c
       a[lane] = s;
     });
   }
+#if MB_CALC_IMPULSE_COM
+  if (has_impulse_com(b)) {  // CostModelImpulseCoM: r = Jcom (v+ - v), from v+ (in a)
+    ex.run([&](int lane) { impulse_com_calc_bodies(b, W, x, a, lane); });
+    ex.run([&](int lane) { impulse_com_calc_value(b, W, cv, lane); });
+  }
+#endif
   const double dt = b.dt;
   if (!ok)  // a singular mass matrix / Schur complement surfaces as forward_error
     ex.run([&](int i) {
@@ -1033,7 +1039,7 @@ MB_HD __forceinline__ double knot_calc_dense_x(const X& ex, const double* P, int
     ok = gauss_jordan<1>(ex, S, nc, nc, nc + 1, flag, pb) && ok;
     ex.run([&](int lane) {
       const int kf = lane - 64;
-      if (kf >= 0 && kf < b.ncost && !imp) {
+      if (kf >= 0 && kf < b.ncost) {
         const double* cr = b.C;
         for (int k = 0; k < kf; ++k) cr += CRec{cr}.size();
         const CRec C{cr};
@@ -1049,6 +1055,12 @@ MB_HD __forceinline__ double knot_calc_dense_x(const X& ex, const double* P, int
       a[lane] = s;
     });
   }
+#if MB_CALC_IMPULSE_COM
+  if (has_impulse_com(b)) {  // CostModelImpulseCoM: r = Jcom (v+ - v), from v+ (in a)
+    ex.run([&](int lane) { impulse_com_calc_bodies(b, W, x, a, lane); });
+    ex.run([&](int lane) { impulse_com_calc_value(b, W, cv, lane); });
+  }
+#endif
   const double dt = b.dt;
   if (!ok)
     ex.run([&](int i) {
@@ -1145,6 +1157,9 @@ constexpr int kSpillBlocks = 1, kSpillJ = 2, kSpillF = 4;
 // residuals (6 per cost), Jexp6 / Ad(exp6^-1) (72)
 // Cost-derivative area (doubles) for nrows stacked residual rows over L + nu columns.
 constexpr int kMaxCostRows = 64;
+// source code of a stacked residual row (the cost table's csrc): jac cost f, row e as 8 f + e,
+// plus kImpulseComSrc on the rows of an impulse CoM cost; force cost row e as -1 - e
+constexpr int kImpulseComSrc = 1024;
 // (4 columns of slack: the GEMM reads rows four columns at a time)
 MB_HD __forceinline__ int cost_rows_ld(int nj, int nu) { return (int)pad2(2 * nj + nu) + 4; }
 constexpr int kMaxCostCols = 3 * kMaxJ;  // diagonal terms per column of [x tangent | u]
@@ -1692,7 +1707,8 @@ MB_HD inline void jac_lane(const Blk& b, const WVals& W, const double* x, int j,
   for (int k = 0; k < b.ncost && only != -2; ++k) {
     const CRec C{cr};
     const int t = C.type();
-    if (jac_cost(b, t) && only >= 0 && f != only) {
+    // (the impulse CoM cost's slot: impulse_com_lane, after the RNEA at v+ - v)
+    if (jac_cost(b, t) && (t == C_IMPULSE_COM || (only >= 0 && f != only))) {
       ++f;
     } else if (jac_cost(b, t)) {
       double r[6] = {0., 0., 0., 0., 0., 0.}, Jc[6] = {0., 0., 0., 0., 0., 0.};
@@ -1766,6 +1782,59 @@ MB_HD inline void jac_lane(const Blk& b, const WVals& W, const double* x, int j,
         for (int r = 0; r < 3; ++r) Ai[(c + 3) * 6 + r] = -o[r];
       }
     }
+  }
+}
+
+// lane j < nj of an impulse knot: column j of every impulse CoM cost's slot (jac cost f):
+// rows 0..2 d(Jcom(q) w)/dq_j at w = v+ - v held fixed, rows 3..5 Jcom's column j; on lane 0
+// the residual Jcom w (rf[6 f + e]). W.a holds the bodies' velocities under w (the impulse
+// RNEA(q, 0, w) without gravity has V = 0, so its accelerations are sum S_k w_k). Turning q_j
+// moves the subtree of j rigidly: dV_b = S_j x (V_b - V_P), dc_b = S_j.lin + S_j.ang x c_b, and
+// the body's CoM velocity p_b = V_b.lin + V_b.ang x c_b changes by
+// dV_b.lin + dV_b.ang x c_b + V_b.ang x dc_b.
+MB_HD inline void impulse_com_lane(const Blk& b, const WVals& W, int j, double* Jf, int jw, double* rf) {
+  const int nj = b.nj;
+  const double* cr = b.C;
+  int f = 0;
+  for (int k = 0; k < b.ncost; ++k) {
+    const CRec C{cr};
+    const int t = C.type();
+    if (t == C_IMPULSE_COM) {
+      double S[6], VP[6], AP[6], dq[3] = {0., 0., 0.}, r[3] = {0., 0., 0.}, mt = 0.;
+      for (int e = 0; e < 6; ++e) S[e] = W.S(j)[e];
+      parent_motion(b, W, j, VP, AP);
+      for (int bb = 0; bb < nj; ++bb) {
+        if (!carries_body(b, bb)) continue;
+        const double mk = *W.m(bb);
+        mt += mk;
+        double V[6], c[3], t1[3];
+        for (int e = 0; e < 6; ++e) V[e] = W.a(bb)[e];
+        for (int e = 0; e < 3; ++e) c[e] = W.c(bb)[e];
+        if (j == 0) {
+          cross3(V + 3, c, t1);
+          for (int e = 0; e < 3; ++e) r[e] += mk * (V[e] + t1[e]);
+        }
+        if (!((*W.anc(bb) >> j) & 1ull)) continue;
+        double D[6], dV[6], dc[3], t2[3];
+        for (int e = 0; e < 6; ++e) D[e] = V[e] - AP[e];
+        cross_m(S, D, dV);
+        cross3(S + 3, c, dc);
+        for (int e = 0; e < 3; ++e) dc[e] += S[e];
+        cross3(dV + 3, c, t1);
+        cross3(V + 3, dc, t2);
+        for (int e = 0; e < 3; ++e) dq[e] += mk * (dV[e] + t1[e] + t2[e]);
+      }
+      double tt[3];
+      cross3(S + 3, W.ch(j), tt);
+      const double m = *W.cm(j);
+      for (int e = 0; e < 3; ++e) {
+        Jf[((int64_t)f * 6 + e) * jw + j] = dq[e] / mt;
+        Jf[((int64_t)f * 6 + 3 + e) * jw + j] = (m * S[e] + tt[e]) / mt;
+        if (j == 0) rf[6 * f + e] = r[e] / mt;
+      }
+    }
+    if (jac_cost(b, t)) ++f;
+    cr += C.size();
   }
 }
 
@@ -1965,7 +2034,7 @@ __device__ __attribute__((noinline)) void da_fx_mfma(const mb_lds_d* Minv, int l
       if (ffe && ti == 0)
 #pragma unroll
         for (int r = 0; r < 6; ++r) d6[r] = __shfl(dav, (lane & 48) | r);
-      if (i >= nj && i < NR && c < L) dfx[(i - nj) * L + c] = acc[q];
+      if (i >= nj && i < NR && c < vcols) dfx[(i - nj) * L + c] = acc[q];
       if (i >= nj || c >= L) continue;
       double fq, fv;  // Fx(i, c), Fx(nj + i, c)
       if (imp) {  // [[I, 0], [-G dtau_dq - H dv0_dq, G M = I - H Jc]]
@@ -2127,6 +2196,42 @@ __device__ __forceinline__ void subtree_nh_mfma(const Blk& b, const WVals& W, co
   }
 }
 #endif
+
+// The rows of the impulse CoM costs in the stacked R (lane's entries e = lane (mod nt)):
+// d(Jcom w)/dq + Jcom dv+/dq | Jcom (dv+/dv - I), with dv+/dx the bottom rows of Fx (device:
+// the block the da product has written, column-major 2 nj x 2 nj; host: from da and H Jc).
+// Jf: the jac-cost slots (rows 0..2 d(Jcom w)/dq, 3..5 Jcom).
+MB_HD inline void impulse_com_rows(int lane, int nt, const double* csrc, const double* Jf, int jw, double* Rm,
+                                            int ldR, int nrows, int nj, int nc, const double* Fx, const double* da,
+                                            int Ld, const double* H, const double* Jc, bool ok) {
+  const int L = 2 * nj, ne = nrows * ldR;
+  for (int e = lane; e < ne; e += nt) {
+    const int row = e / ldR, c = e % ldR;
+    const int src = (int)mb_lds(csrc)[row];
+    if (src < kImpulseComSrc || c >= L) continue;
+    const int f = (src - kImpulseComSrc) >> 3, e2 = src & 7;
+    const double* Jm = Jf + ((int64_t)f * 6 + 3 + e2) * jw;
+    double v = c < nj ? Jf[((int64_t)f * 6 + e2) * jw + c] : -Jm[c - nj];
+#if defined(__HIP_DEVICE_COMPILE__)
+    const mb_glb_d* Fc = (const mb_glb_d*)Fx + ((int64_t)c * L + nj);
+    for (int i = 0; i < nj; ++i) v += Jm[i] * Fc[i];
+    (void)nc, (void)da, (void)Ld, (void)H, (void)Jc, (void)ok;
+#else
+    for (int i = 0; i < nj; ++i) {
+      double fv;
+      if (c < nj) {
+        fv = da[(int64_t)i * Ld + c];
+      } else {
+        double s = 0.;
+        for (int k = 0; k < nc; ++k) s += H[(int64_t)k * nj + i] * Jc[(int64_t)k * nj + (c - nj)];
+        fv = ok ? (c - nj == i ? 1. : 0.) - s : NAN;
+      }
+      v += Jm[i] * fv;
+    }
+#endif
+    mb_lds(Rm)[e] = v;
+  }
+}
 
 // SP: the spilled plan fixed at compile time (0 / 1: the device kernels, one variant per
 // plan) or taken from `spill` (-1: the host emulation)
@@ -2369,6 +2474,20 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
         for (int k = 0; k < b.ncost; ++k) {
           const CRec C{cr};
           if (force_cost(C.type())) cc += C.weight() * force_cost_activation(b, C, lam, nu);
+          if (C.type() == C_IMPULSE_COM) {  // Jcom (v+ - v) from the bodies' velocities in W.a
+            double r[3] = {0., 0., 0.}, mt = 0., a = 0.;
+            for (int bb = 0; bb < nj; ++bb) {
+              if (!carries_body(b, bb)) continue;
+              const double mk = *W.m(bb);
+              double t1[3];
+              cross3(W.a(bb) + 3, W.c(bb), t1);
+              mt += mk;
+              for (int e = 0; e < 3; ++e) r[e] += mk * (W.a(bb)[e] + t1[e]);
+            }
+            const Act act = cost_act(b, C, nu);
+            for (int e = 0; e < 3; ++e) a += act.value2(e, r[e] / mt);
+            cc += C.weight() * (0.5 * a);
+          }
           cr += C.size();
         }
         *cost_out = dt != 0. ? dt * cc : cc;
@@ -2423,7 +2542,12 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
     for (int j = lane - h; j < nj; j += ex.nt - h) jac_lane(b, W, x, j, Jf, jw, rf, ffe ? dq : nullptr, Je, Ai);
   });
   if (imp) {  // V = 0 in the impulse RNEA: P_k = 0, Q_k = Ycrb_k S_k
+    // (beside it, from the second wave on: the impulse CoM costs' Jacobian slots and residuals,
+    // from the bodies' velocities under v+ - v that the RNEA above left in W.a)
+    const bool icom = has_impulse_com(b);
     ex.run([&](int lane) {
+      if (icom)
+        for (int j = lane - 64; j >= 0 && j < nj; j += ex.nt - 64) impulse_com_lane(b, W, j, Jf, jw, rf);
       if (lane >= nj) return;
       comp_mul(W, lane, W.S(lane), qp + 12 * lane);
       for (int e = 0; e < 6; ++e) qp[12 * lane + 6 + e] = 0.;
@@ -2455,7 +2579,9 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
   }
   // d lambda / dx, d lambda / du for CostModelContactForce (contact-fwddyn.hxx:131-137, with
   // enable_force): Kinv bottom-left = H^T, bottom-right = -S^-1; dtau/du = [0; I]
-  const bool fd = b.enable_force && nc > 0 && !imp;
+  // (impulse knots, section flag 3: d Lambda / dx = [H^T dtau_dq - S^-1 dv0_dq, -S^-1 Jc], the
+  // exact derivative at r_coeff = 0, the restitution terms dropped otherwise as in Fx; no du)
+  const bool fd = b.enable_force && nc > 0;
   // (kSpillF: in the knot's Fu block, written last)
   double* dfx = (spill & kSpillF) ? Fu : w + l.dfx;
   double* dfu = (spill & kSpillF) ? Fu + pad2((int64_t)nc * L) : w + l.dfu;
@@ -2527,12 +2653,26 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
 #endif
     if (fd) {
       const double* Sinv = Sx + (int64_t)nc * nc;
-      for (int e = lane; e < (dfx_done ? 0 : nc * L); e += ex.nt) {
-        const int k = e / L, c = e % L;
+      for (int e = lane; e < (dfx_done ? 0 : nc * (imp ? nj : L)); e += ex.nt) {
+        const int k = e / (imp ? nj : L), c = e % (imp ? nj : L);
         double s = 0.;
         for (int i = 0; i < nj; ++i) s += H[(int64_t)k * nj + i] * dtau[(int64_t)i * L + c];
         for (int m2 = 0; m2 < nc; ++m2) s -= Sinv[(int64_t)m2 * nc + k] * da0[(int64_t)m2 * L + c];
-        dfx[e] = s;
+        dfx[(int64_t)k * L + c] = s;
+      }
+      if (imp) {  // d Lambda / dv = -H^T M = -S^-1 Jc (no dtau / dv0 columns there)
+        const double* const SiL = ex.lds(Sinv);
+        const double* const JcL = ex.lds(Jc);
+        for (int e = lane; e < nc * nj; e += ex.nt) {
+          const int k = e / nj, c = e % nj;
+          double s = 0.;
+          for (int m2 = 0; m2 < nc; ++m2) s -= SiL[(int64_t)m2 * nc + k] * JcL[(int64_t)m2 * nj + c];
+          const int64_t o = (int64_t)k * L + nj + c;
+          if (spill & kSpillF)  // (the Fu block: a global store; else LDS)
+            mb_gstore(dfx + o, s);
+          else
+            ex.lds(dfx)[o] = s;
+        }
       }
       for (int e = lane; e < nc * nj; e += ex.nt) {
         const int k = e / nj, c = e % nj;
@@ -2581,7 +2721,9 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
             ch[row] = act.hess(e, rv);
             cam[row] = act.kind <= A_WEIGHTED_QUAD ? act.p[e] : 1.;
             cav[row] = act.kind <= A_WEIGHTED_QUAD ? rv : act.sgrad(e, rv, 1.);
-            csrc[row] = (double)(f * 8 + e);
+            // (the impulse CoM cost's rows marked in the source itself: the rows phase tells
+            // them apart without a look at the group table)
+            csrc[row] = (double)((t == C_IMPULSE_COM ? kImpulseComSrc : 0) + f * 8 + e);
             cgi[row] = g;
           }
           cg[4 * g] = r0;
@@ -2710,7 +2852,9 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
       const int src = (int)csrc[row];
       double v = 0.;
       if (src >= 0) {  // jac cost f, row e2
-        const int f = src >> 3, e2 = src & 7;
+        // (an impulse CoM cost's row, src >= kImpulseComSrc: its slot's first rows as a
+        // placeholder here, the row itself formed after these, below)
+        const int f = (src & (kImpulseComSrc - 1)) >> 3, e2 = src & 7;
         const bool xc = c < nj || (c < L && jw == L);
         v = xc ? Jf[((int64_t)f * 6 + e2) * jw + c] : 0.;
         // a q-only cost stored with jw = L carries zeros in its velocity columns
@@ -2745,6 +2889,9 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
 #endif
       }
     }
+    // the rows of the impulse CoM costs, after the others and only on a knot that has one (the
+    // branch is uniform); each entry on the lane that stored its placeholder above
+    if (imp && has_impulse_com(b)) impulse_com_rows(lane, ex.nt, csrc, Jf, jw, Rm, ldR, nrows, nj, nc, Fx, da, Ld, H, Jc, ok);
 #if defined(__HIP_DEVICE_COMPILE__)
     // the diagonal terms of the state / control costs (beyond the free-flyer block), per
     // column of [x tangent | u], in cost order

@@ -49,9 +49,14 @@ class SimpleBipedGaitProblem:
     """Defines a simple 3d locomotion problem (utils/biped.py:6-308). ``copSupport`` =
     (L, W), the feet's extent along their frames' x and y, adds a
     CostModelContactCoPPosition (weight ``copWeight``) on every support foot, as the
-    reference fork's humanoid walks do (contact-cop-position.hpp); None: no such cost."""
+    reference fork's humanoid walks do (contact-cop-position.hpp); None: no such cost.
+    ``impulseCosts``: createImpulseModel adds a CostModelImpulseFrictionCone (1e1) on every
+    support foot and, with ``copSupport``, a CostModelImpulseCoPPosition (``copWeight``), and
+    computes the multiplier Jacobians they read (enable_force). ``pseudoImpulse``: what the
+    foot switches of the walking gait are (biped.py:218-229 takes the pseudo-impulse)."""
 
-    def __init__(self, rmodel, rightFoot, leftFoot, copSupport=None, copWeight=1e1):
+    def __init__(self, rmodel, rightFoot, leftFoot, copSupport=None, copWeight=1e1, impulseCosts=False,
+                 pseudoImpulse=True):
         self.rmodel = rmodel
         self.state = mb.StateMultibody(self.rmodel)
         self.actuation = mb.ActuationModelFloatingBase(self.state)
@@ -64,6 +69,8 @@ class SimpleBipedGaitProblem:
         self.nsurf = np.array([0., 0., 1.])
         self.copSupport = None if copSupport is None else np.array(copSupport, float).reshape(2)
         self.copWeight = float(copWeight)
+        self.impulseCosts = bool(impulseCosts)
+        self.pseudoImpulse = bool(pseudoImpulse)
 
     def createWalkingModels(self, x0, stepLength, stepHeight, timeStep, stepKnots, supportKnots):
         """The running models of createWalkingProblem (biped.py:25-65)."""
@@ -153,7 +160,7 @@ class SimpleBipedGaitProblem:
             footSwingModel += [
                 self.createSwingFootModel(timeStep, supportFootIds, comTask=comTask, swingFootTask=swingFootTask)
             ]
-        footSwitchModel = self.createFootSwitchModel(supportFootIds, swingFootTask)
+        footSwitchModel = self.createFootSwitchModel(supportFootIds, swingFootTask, self.pseudoImpulse)
         comPos0 += [stepLength * comPercentage, 0., 0.]
         for p in feetPos0:
             p += [stepLength, 0., 0.]
@@ -243,7 +250,15 @@ class SimpleBipedGaitProblem:
                 costModel.addCost(self.rmodel.frames[i.id][0] + "_footTrack", footTrack, 1e8)
         stateWeights = np.array([1.] * 6 + [0.1] * (self.rmodel.nv - 6) + [10] * self.rmodel.nv)
         costModel.addCost("stateReg", self._stateReg(stateWeights, 0), 1e1)
-        return mb.ActionModelImpulseFwdDynamics(self.state, impulseModel, costModel)
+        if self.impulseCosts:
+            for i in supportFootIds:
+                cone = mb.FrictionCone(self.nsurf, self.mu, 4, False)
+                costModel.addCost(self.rmodel.frames[i][0] + "_impulseFrictionCone",
+                                  mb.CostModelImpulseFrictionCone(self.state, mb.FrameFrictionCone(i, cone)), 1e1)
+                if self.copSupport is not None:
+                    costModel.addCost(self.rmodel.frames[i][0] + "_impulseCoP", mb.CostModelImpulseCoPPosition(
+                        self.state, mb.FrameCoPSupport(i, self.copSupport)), self.copWeight)
+        return mb.ActionModelImpulseFwdDynamics(self.state, impulseModel, costModel, 0., 0., self.impulseCosts)
 
 
 class SimpleQuadrupedalGaitProblem:
@@ -483,8 +498,11 @@ class SimpleQuadrupedalGaitProblem:
                                                               0., True)
         return IntegratedActionModelEuler(dmodel, 0.)
 
-    def createImpulseModel(self, supportFootIds, swingFootTask, JMinvJt_damping=1e-12, r_coeff=0.0):
-        """quadruped.py:522-553: ImpulseModel3D on the support feet."""
+    def createImpulseModel(self, supportFootIds, swingFootTask, JMinvJt_damping=1e-12, r_coeff=0.0,
+                           impulseCosts=False):
+        """quadruped.py:522-553: ImpulseModel3D on the support feet. ``impulseCosts`` adds a
+        CostModelImpulseFrictionCone (1e1) on every support foot, with the multiplier Jacobians
+        it reads (enable_force)."""
         impulseModel = mb.ImpulseModelMultiple(self.state)
         for i in supportFootIds:
             impulseModel.addImpulse(self.rmodel.frames[i][0] + "_impulse", mb.ImpulseModel3D(self.state, i))
@@ -497,7 +515,12 @@ class SimpleQuadrupedalGaitProblem:
         nv = self.rmodel.nv
         stateWeights = np.array([1.] * 6 + [10.] * (nv - 6) + [10.] * nv)
         costModel.addCost("stateReg", self._stateReg(stateWeights, 0), 1e1)
-        model = mb.ActionModelImpulseFwdDynamics(self.state, impulseModel, costModel)
+        if impulseCosts:
+            for i in supportFootIds:
+                cone = mb.FrictionCone(self.nsurf, self.mu, 4, False)
+                costModel.addCost(self.rmodel.frames[i][0] + "_impulseFrictionCone",
+                                  mb.CostModelImpulseFrictionCone(self.state, mb.FrameFrictionCone(i, cone)), 1e1)
+        model = mb.ActionModelImpulseFwdDynamics(self.state, impulseModel, costModel, 0., 0., bool(impulseCosts))
         model.JMinvJt_damping = JMinvJt_damping
         model.r_coeff = r_coeff
         return model

@@ -42,6 +42,7 @@ COST_FRICTION_CONE = 9
 COST_FRAME_VELOCITY = 10
 COST_COP_POSITION = 11
 COST_FRAME_ROTATION = 12
+COST_IMPULSE_COM = 13
 MAX_CONTACT_ROWS = 24
 MAX_DOFS = 64  # nv of the device path (one lane per tangent direction of a wave pair)
 
@@ -1134,6 +1135,91 @@ class CostModelContactCoPPosition(_Cost):
         return [np.concatenate([[-1.0, 0.0, A.shape[0]], A.reshape(-1)]).reshape(1, -1)]
 
 
+class CostModelContactImpulse(CostModelContactForce):
+    """r = Lambda_frame - fref (impulse costs of the reference: contact-impulse.hxx): the
+    multipliers of the impulse on frame fref.id of an ActionModelImpulseFwdDynamics (3 rows
+    on an ImpulseModel3D, 6 on a 6D); nu = 0. Rx is the matching rows of
+    d Lambda / dx = [H^T dtau_dq - S^-1 dv0_dq, -S^-1 Jc], computed only with
+    enable_force=True (zero otherwise): the exact derivative at r_coeff = 0, the
+    restitution terms dropped otherwise, as in the knot's Fx. The record is the contact
+    class's (type 7), valid on impulse knots only. Parity unpinned against the reference
+    binary."""
+
+    impulse_cost = True
+
+    def __init__(self, state, a, b=None):
+        """(state, activation, fref) | (state, fref, nr=6): no control dimension to pass."""
+        if isinstance(a, _ACTIVATIONS):
+            if not isinstance(b, FrameForce):
+                raise TypeError("CostModelContactImpulse(state, activation, fref) needs a FrameForce reference")
+            super().__init__(state, a, b, 0)
+        elif isinstance(a, FrameForce):
+            nr = 6 if b is None else b
+            if isinstance(nr, bool) or not isinstance(nr, (int, np.integer)):
+                raise TypeError("CostModelContactImpulse(state, fref, nr): nr is 3 or 6")
+            super().__init__(state, a, int(nr), 0)
+        else:
+            raise TypeError("CostModelContactImpulse(state, activation, fref) | (state, fref, nr=6)")
+
+
+class CostModelImpulseFrictionCone(CostModelContactFrictionCone):
+    """r = A Lambda_lin (impulse-friction-cone.hxx): the cone matrix times the linear
+    multipliers of the impulse on frame fref.id; nu = 0. Rx = A d Lambda_lin / dx with
+    enable_force=True (zero otherwise; see CostModelContactImpulse). The record is the
+    contact class's (type 9), valid on impulse knots only. Without an activation it takes
+    the cone's barrier, ActivationModelQuadraticBarrier(ActivationBounds(cone.lb, cone.ub)).
+    Parity unpinned against the reference binary."""
+
+    impulse_cost = True
+
+    def __init__(self, state, a, b=None):
+        """(state, activation, fref) | (state, fref)."""
+        act, fref = (a, b) if isinstance(a, _ACTIVATIONS) else (None, a)
+        if not isinstance(fref, FrameFrictionCone) or (act is None and b is not None):
+            raise TypeError("CostModelImpulseFrictionCone(state, activation, fref) | (state, fref)")
+        if act is None:
+            act = ActivationModelQuadraticBarrier(ActivationBounds(fref.cone.lb, fref.cone.ub))
+        super().__init__(state, act, fref, 0)
+
+
+class CostModelImpulseCoPPosition(CostModelContactCoPPosition):
+    """r = A Lambda (impulse-cop-position.hpp of the reference fork): the support matrix of
+    cop_support times the six multipliers of the ImpulseModel6D on frame cop_support.id;
+    nu = 0; a (0, DBL_MAX) barrier by default. Rx = A d Lambda / dx with enable_force=True
+    (zero otherwise; see CostModelContactImpulse). The record is the contact class's
+    (type 11), valid on impulse knots only. Parity unpinned against the reference binary."""
+
+    impulse_cost = True
+
+    def __init__(self, state, a, b=None):
+        """(state, activation, cop_support) | (state, cop_support)."""
+        act, ref = (a, b) if isinstance(a, _ACTIVATIONS) else (None, a)
+        if not isinstance(ref, FrameCoPSupport) or (act is None and b is not None):
+            raise TypeError("CostModelImpulseCoPPosition(state, activation, cop_support) | (state, cop_support)")
+        super().__init__(state, *([act] if act is not None else []), ref, 0)
+
+
+class CostModelImpulseCoM(_Cost):
+    """r = Jcom(q) (v+ - v) (impulse-com.hxx): the change of the CoM velocity over the
+    impulse of an ActionModelImpulseFwdDynamics; overloads (state) and (state, activation)
+    with ActivationModelQuad(3) by default; nu = 0. Rx = [d(Jcom(q) w)/dq at w = v+ - v fixed
+    + Jcom dv+/dq, Jcom (dv+/dv - I)] with dv+/dx the bottom rows of the knot's Fx (so it
+    inherits Fx's restitution convention); it does not depend on enable_force. Record type
+    13, an empty payload, valid on impulse knots only. Parity unpinned against the reference
+    binary."""
+
+    type = COST_IMPULSE_COM
+    impulse_cost = True
+
+    def __init__(self, state, activation=None):
+        if activation is not None and not isinstance(activation, _ACTIVATIONS):
+            raise TypeError("CostModelImpulseCoM(state[, activation])")
+        super().__init__(state, activation, 3, 0)
+
+    def _payload(self):
+        return []
+
+
 class CostModelFrameVelocity(_Cost):
     """r = v_f - vref (frame-velocity.hxx:53-84): the LOCAL spatial velocity of frame
     vref.id (pinocchio::getFrameVelocity) minus the reference motion; Rx =
@@ -1280,9 +1366,16 @@ class DifferentialActionModelFreeFwdDynamics(_ControlLimits):
     def pack_body(self, dt):
         """(Bm, size) rows of the FDDP_KNOT_EULER_FREEFWD block for step dt (with a
         floating-base actuation: the FDDP_KNOT_EULER_CONTACTFWD block, no contacts)."""
+        _refuse_impulse_costs(self.costs)
         if isinstance(self.actuation, ActuationModelFloatingBase):
             return _pack_mb(self.state, self._armature, self.costs, dt, [self.actuation.nun, 0.0, 0.0, 0.0])
         return _pack_mb(self.state, self._armature, self.costs, dt)
+
+
+def _refuse_impulse_costs(costs):
+    """The Impulse* costs read an impulse knot's multipliers: a differential model has none."""
+    if any(it.active and getattr(it.cost, "impulse_cost", False) for it in costs.costs.values()):
+        raise ValueError("Invalid argument: impulse costs need an ActionModelImpulseFwdDynamics")
 
 
 def _pack_mb(state, armature, costs, dt, section=None):
@@ -1479,6 +1572,7 @@ class DifferentialActionModelContactFwdDynamics(DifferentialActionModelFreeFwdDy
         """(Bm, size) rows of the FDDP_KNOT_EULER_CONTACTFWD block: the
         FDDP_KNOT_EULER_FREEFWD layout, then [nun, damping, ncontact, flag] and the
         active contact records in name order."""
+        _refuse_impulse_costs(self.costs)
         recs = self.contacts.pack()
         if self.contacts.nc > MAX_CONTACT_ROWS:
             raise ValueError(f"Invalid argument: the device path holds at most {MAX_CONTACT_ROWS} contact rows")
@@ -1497,29 +1591,37 @@ class DifferentialActionModelContactFwdDynamics(DifferentialActionModelFreeFwdDy
         for n in self.contacts.inactive:
             c = self.contacts.contacts[n].contact
             rows.setdefault(c._ref.id, (INACTIVE_FORCE_ROW, c.nc))
-        o = _abi.PARAM_HEADER + 3 + self.state.nv + JOINT_REC * (self.state.pinocchio.njoints - 1)
-        for name in sorted(self.costs.costs):
-            it = self.costs.costs[name]
-            if not it.active:
-                continue
-            size = int(out[0, o + 3])
-            if it.cost.type in (COST_CONTACT_FORCE, COST_FRICTION_CONE, COST_COP_POSITION):
-                fid = it.cost.frame_id
-                if fid not in rows:
-                    raise ValueError(f"Invalid argument: there is not contact defined for frame {fid}")
-                row0, nci = rows[fid]
-                if it.cost.type == COST_CONTACT_FORCE and nci != it.cost.activation.nr:
-                    raise ValueError("Invalid argument: the contact-force cost and its contact differ in size")
-                if it.cost.type == COST_COP_POSITION and nci != 6:
-                    raise ValueError("Invalid argument: the CoP position cost needs a ContactModel6D on its frame")
-                out[:, o + COST_HDR] = row0
-                if it.cost.type in (COST_FRICTION_CONE, COST_COP_POSITION):
-                    out[:, o + COST_HDR + 1] = nci
-            o += size
+        _resolve_force_rows(out, self.state, self.costs, rows, "contact")
         return out
 
 
-INACTIVE_FORCE_ROW = -2  # contact exists but is inactive: lambda = 0, zero force Jacobians
+INACTIVE_FORCE_ROW = -2  # contact / impulse exists but is inactive: lambda = 0, zero force Jacobians
+_FORCE_COSTS = (COST_CONTACT_FORCE, COST_FRICTION_CONE, COST_COP_POSITION)
+
+
+def _resolve_force_rows(out, state, costs, rows, what):
+    """Write row0 (and the row count of a cone / CoP record) of every force cost of a packed
+    block: rows maps a frame id to (row0, rows) of the contact / impulse (`what`) on it."""
+    o = _abi.PARAM_HEADER + 3 + state.nv + JOINT_REC * (state.pinocchio.njoints - 1)
+    model6 = "ContactModel6D" if what == "contact" else "ImpulseModel6D"
+    for name in sorted(costs.costs):
+        it = costs.costs[name]
+        if not it.active:
+            continue
+        size = int(out[0, o + 3])
+        if it.cost.type in _FORCE_COSTS:
+            fid = it.cost.frame_id
+            if fid not in rows:
+                raise ValueError(f"Invalid argument: there is not {what} defined for frame {fid}")
+            row0, nci = rows[fid]
+            if it.cost.type == COST_CONTACT_FORCE and nci != it.cost.activation.nr:
+                raise ValueError(f"Invalid argument: the {what}-force cost and its {what} differ in size")
+            if it.cost.type == COST_COP_POSITION and nci != 6:
+                raise ValueError(f"Invalid argument: the CoP position cost needs a {model6} on its frame")
+            out[:, o + COST_HDR] = row0
+            if it.cost.type in (COST_FRICTION_CONE, COST_COP_POSITION):
+                out[:, o + COST_HDR + 1] = nci
+        o += size
 
 
 class _Impulse:
@@ -1657,7 +1759,7 @@ class ActionModelImpulseFwdDynamics(_impulse_model_base()):
     @property
     def _version(self):
         return (self.__dict__.get("_own_version", 0), self.state.pinocchio._version, self.costs._version,
-                self.impulses._version, self._arm_version, self.r_coeff, self.JMinvJt_damping,
+                self.impulses._version, self._arm_version, self.r_coeff, self.JMinvJt_damping, self.enable_force,
                 tuple(getattr(c.cost, "_version", 0) for c in self.costs.costs.values()))
 
     @_version.setter
@@ -1669,11 +1771,27 @@ class ActionModelImpulseFwdDynamics(_impulse_model_base()):
 
     def pack(self):
         recs = self.impulses.pack()
-        if any(it.active and it.cost.type in (COST_FRAME_VELOCITY, COST_CONTACT_FORCE, COST_FRICTION_CONE,
-                                              COST_COP_POSITION)
+        # the contact classes read a contact's data collector, which an impulse knot has not
+        # (their Impulse* twins read the impulses'); frame velocities are not covered here
+        if any(it.active and (it.cost.type == COST_FRAME_VELOCITY or
+                              (it.cost.type in _FORCE_COSTS and not getattr(it.cost, "impulse_cost", False)))
                for it in self.costs.costs.values()):
             raise NotImplementedError("crocoddyl_amd: frame-velocity / force costs on impulse knots are not covered")
         if self.impulses.ni > MAX_CONTACT_ROWS:
             raise ValueError(f"Invalid argument: the device path holds at most {MAX_CONTACT_ROWS} impulse rows")
-        sec = np.concatenate([[self.r_coeff, self.JMinvJt_damping, len(recs), 1.0]] + recs)
-        return self.kind, 0, _pack_mb(self.state, self._armature, self.costs, 0.0, sec)
+        sec = np.concatenate([[self.r_coeff, self.JMinvJt_damping, len(recs), 3.0 if self.enable_force else 1.0]]
+                             + recs)
+        out = _pack_mb(self.state, self._armature, self.costs, 0.0, sec)
+        # costs on an impulse's multipliers: the row offset of the impulse on the cost's frame
+        # among the active impulses (the first match in name order); an impulse that exists
+        # but is inactive has Lambda = 0 and zero Jacobians
+        rows, r0 = {}, 0
+        for n in self.impulses.active:
+            c = self.impulses.impulses[n].impulse
+            rows.setdefault(c.frame, (r0, c.ni))
+            r0 += c.ni
+        for n in self.impulses.inactive:
+            c = self.impulses.impulses[n].impulse
+            rows.setdefault(c.frame, (INACTIVE_FORCE_ROW, c.ni))
+        _resolve_force_rows(out, self.state, self.costs, rows, "impulse")
+        return self.kind, 0, out

@@ -32,7 +32,9 @@ calcDiff (contact-fwddyn.hxx:107-160, euler.hxx:83-131, cost-sum.hxx:122-160), a
     Gauss-Newton products R^T diag(w h) R over each cost's columns c: nr c (c + 1)
     (symmetric half), gradients 2 nr c; state / control costs 4 per entry.
 Impulse knots (impulse-fwddyn.hxx) take the calc's and calcDiff's contact terms with
-the impulse rows; free-dynamics knots nc = 0.
+the impulse rows; free-dynamics knots nc = 0. The impulse costs: the multiplier rows as
+the contact costs' (over the x columns), CostModelImpulseCoM 10 n for Jcom (v+ - v) and,
+in calcDiff, Jcom, d(Jcom w)/dq and Jcom times the bottom rows of Fx.
 
 These are estimates of the reference's arithmetic, stated so that the roofline's
 flop fraction can be reproduced; bench.py reports them beside the HBM roofline and
@@ -100,13 +102,19 @@ def _cost_terms(dam, n, nu, L, robot, par):
         elif isinstance(c, mb.CostModelCoMPosition):
             calc += 10 * n
             diff += 10 * n * 3 + nr * n * (n + 1) + 2 * nr * n
+        elif isinstance(c, mb.CostModelImpulseCoM):
+            # Jcom (v+ - v); Jcom, d(Jcom w)/dq (a cross product chain per dof), Jcom times the
+            # bottom rows of Fx (3 x n x L), Gauss-Newton over the x columns
+            calc += 10 * n
+            diff += 10 * n * 3 + 3 * C_CR * n + 2 * 3 * n * L + nr * L * (L + 1) + 2 * nr * L
         elif isinstance(c, mb.CostModelState):
             calc += 2 * L + (100 if robot.has_freeflyer else 0)
             diff += 4 * L + (72 * 6 if robot.has_freeflyer else 0)
         elif isinstance(c, mb.CostModelControl):
             calc += 2 * nu
             diff += 4 * nu
-        else:  # contact force / friction cone / CoP position: rows of lambda and d lambda / d(x, u)
+        else:  # contact force / friction cone / CoP position (their impulse twins: nu = 0): rows of
+            # lambda and d lambda / d(x, u)
             cols = L + nu
             diff += nr * cols * (cols + 1) + 2 * nr * cols
     return calc, diff

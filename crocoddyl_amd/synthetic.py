@@ -36,7 +36,7 @@ CONFIGS = {
 }
 
 
-def gait_models(name, T=None, copSupport=None):
+def gait_models(name, T=None, copSupport=None, impulseCosts=False, pseudoImpulse=True):
     """(gait builder, running models, terminal model) of a gait config. The knot
     counts are the reference benchmark's gait parameters stretched to the config's
     T: Talos walking (benchmark/bipedal_walk_optctrl.py:82-90: step 0.6 m / 0.1 m,
@@ -44,13 +44,14 @@ def gait_models(name, T=None, copSupport=None):
     (benchmark/quadrupedal_gaits_optctrl.py:134-142: step 0.15 m / 0.1 m, dt 1e-2,
     2 support knots) with 27 step knots -> T = 60. A smaller T shortens the steps
     (for parity tests). ``copSupport`` = (L, W): the biped's feet get a
-    CostModelContactCoPPosition each (gaits.SimpleBipedGaitProblem)."""
+    CostModelContactCoPPosition each (gaits.SimpleBipedGaitProblem); ``impulseCosts`` /
+    ``pseudoImpulse``: the biped's foot switches as impulse knots with their impulse costs."""
     from . import gaits, robots
     kind, _, _, T0, _, dt = CONFIGS[name]
     T = T0 if T is None else T
     if kind == "gait_biped":
         g = gaits.SimpleBipedGaitProblem(robots.sample_talos(), "right_sole_link", "left_sole_link",
-                                         copSupport=copSupport)
+                                         copSupport=copSupport, impulseCosts=impulseCosts, pseudoImpulse=pseudoImpulse)
         sk = max(1, T // 2 - 2)
         models = g.createWalkingModels(g.rmodel.defaultState, 0.6, 0.1, dt, sk, 1)
     else:
@@ -61,12 +62,13 @@ def gait_models(name, T=None, copSupport=None):
     return g, models, models[-1]
 
 
-def build_gait(name, T=None, B=None, seed=None, spread=0.02, v_spread=0.1, copSupport=None):
+def build_gait(name, T=None, B=None, seed=None, spread=0.02, v_spread=0.1, copSupport=None, impulseCosts=False,
+               pseudoImpulse=True):
     """(x0s, running, terminal) of a gait config: x0_b = the reference posture
     integrated along a seeded tangent perturbation (q +- spread, v +- v_spread)."""
     _, _, _, T0, B0, _ = CONFIGS[name]
     B = B0 if B is None else B
-    g, running, terminal = gait_models(name, T, copSupport)
+    g, running, terminal = gait_models(name, T, copSupport, impulseCosts, pseudoImpulse)
     rng = np.random.default_rng(seed_of(name) + 1 if seed is None else seed)
     x0 = g.rmodel.defaultState
     nv = g.state.nv
@@ -288,12 +290,36 @@ def _frot_ref(mb):
     return mb._rot_axis(np.array([0.6, 0.0, 0.8]), -0.5)
 
 
+def _impulse_cost_activation(mb, kind, nr, lb, ub):
+    """The activation of a synthetic impulse cost: None (the class's default), "quad", "wquad",
+    "barrier" (bounds lb, ub) or "wbarrier"."""
+    if kind is None:
+        return None
+    w = np.linspace(0.5, 2.0, nr)
+    if kind == "quad":
+        return mb.ActivationModelQuad(nr)
+    if kind == "wquad":
+        return mb.ActivationModelWeightedQuad(w)
+    bounds = mb.ActivationBounds(np.broadcast_to(lb, (nr,)).copy(), np.broadcast_to(ub, (nr,)).copy())
+    if kind == "barrier":
+        return mb.ActivationModelQuadraticBarrier(bounds)
+    return mb.ActivationModelWeightedQuadraticBarrier(bounds, w)
+
+
 def impulse_model(robot=None, kind="6d", r_coeff=0.0, damping=0.0, weighted=False, armature=None, inactive=False,
-                  frot=False):
+                  frot=False, impulse_force=False, impulse_cone=False, impulse_cop=None, impulse_com=False,
+                  cost_act=None, cost_inactive=False, enable_force=None, force_bound=0.5, com_bound=0.02):
     """ActionModelImpulseFwdDynamics on the arm's gripper ("6d": ImpulseModel6D,
     "3d": ImpulseModel3D, "6d+3d": plus a 3D impulse on the elbow frame),
     costs xReg (+ an elbow FrameTranslation when ``weighted``, an elbow
-    CostModelFrameRotation with ``frot``)."""
+    CostModelFrameRotation with ``frot``). The impulse costs: ``impulse_force`` a
+    CostModelContactImpulse per impulse, ``impulse_cone`` a CostModelImpulseFrictionCone per
+    impulse (a tilted surface normal), ``impulse_cop`` = (L, W) a CostModelImpulseCoPPosition
+    on the gripper's 6D impulse, ``impulse_com`` a CostModelImpulseCoM; ``cost_act`` picks
+    their activation (None: each class's default; "quad", "wquad", "barrier", "wbarrier",
+    the barriers at +-``force_bound`` / +-``com_bound`` or the cone's / the support's own
+    bounds); ``cost_inactive`` (with ``inactive``) adds a force cost on the switched-off
+    impulse of the elbow frame. ``enable_force`` defaults to whether a force cost is there."""
     from . import multibody as mb
     model = mb.sample_talos_arm() if robot is None else robot
     if not model.existFrame("elbow_site"):
@@ -315,7 +341,37 @@ def impulse_model(robot=None, kind="6d", r_coeff=0.0, damping=0.0, weighted=Fals
                                                                  0), 0.3)
     if frot:
         costs.addCost("elbowRot", mb.CostModelFrameRotation(state, mb.FrameRotation(eid, _frot_ref(mb)), 0), 0.4)
-    am = mb.ActionModelImpulseFwdDynamics(state, imps, costs, r_coeff, damping)
+    sites = [("gripper", fid, 6 if kinds[0] == "6d" else 3)] + ([("elbow", eid, 3)] if len(kinds) > 1 else [])
+    if impulse_force:
+        for i, (name, f, nr) in enumerate(sites):
+            act = _impulse_cost_activation(mb, cost_act, nr, -force_bound, force_bound)
+            fref = mb.FrameForce(f, (0.3, -0.2, 0.5, 0.02, 0.01, -0.03) if i == 0 else np.zeros(6))
+            costs.addCost(name + "Impulse", mb.CostModelContactImpulse(state, fref, nr) if act is None
+                          else mb.CostModelContactImpulse(state, act, fref), 1e-2)
+    if impulse_cone:
+        cone = mb.FrictionCone(np.array([0.1, -0.2, 1.0]), 0.7, 4, False, 0.5)
+        for name, f, nr in sites:
+            act = _impulse_cost_activation(mb, cost_act, cone.nf + 1, cone.lb, cone.ub)
+            ff = mb.FrameFrictionCone(f, cone)
+            costs.addCost(name + "ICone", mb.CostModelImpulseFrictionCone(state, ff) if act is None
+                          else mb.CostModelImpulseFrictionCone(state, act, ff), 0.1)
+    if impulse_cop is not None:
+        act = _impulse_cost_activation(mb, cost_act, 4, 0.0, mb.DBL_MAX)
+        sup = mb.FrameCoPSupport(fid, impulse_cop)
+        costs.addCost("gripperICoP", mb.CostModelImpulseCoPPosition(state, sup) if act is None
+                      else mb.CostModelImpulseCoPPosition(state, act, sup), 0.2)
+    if impulse_com:
+        act = _impulse_cost_activation(mb, cost_act, 3, -com_bound, com_bound)
+        costs.addCost("comImpulse", mb.CostModelImpulseCoM(state) if act is None
+                      else mb.CostModelImpulseCoM(state, act), 2.0)
+    if cost_inactive:  # on the switched-off "aux" impulse (3D, elbow frame): Lambda = 0, no Jacobians
+        costs.addCost("auxImpulse", mb.CostModelContactImpulse(state, mb.FrameForce(eid, (0.1, 0.2, -0.1, 0, 0, 0)), 3),
+                      1e-2)
+        cone = mb.FrictionCone(np.array([0.0, 0.0, 1.0]), 0.7, 4, False, 0.5)
+        costs.addCost("auxICone", mb.CostModelImpulseFrictionCone(state, mb.FrameFrictionCone(eid, cone)), 0.1)
+    if enable_force is None:
+        enable_force = bool(impulse_force or impulse_cone or impulse_cop is not None or cost_inactive)
+    am = mb.ActionModelImpulseFwdDynamics(state, imps, costs, r_coeff, damping, enable_force)
     if armature is not None:
         am.armature = armature
     return am

@@ -112,6 +112,12 @@ int fddp_abi_version(void);
  *    12 CostModelFrameRotation (frame-rotation.hxx): frame joint, frame
  *       placement R(9) p(3), Rref^T (9, in the order of 3's Mref^-1 R);
  *       r = log3(Rref^T oRf), nr = 3
+ *    13 CostModelImpulseCoM (impulse knots only): empty payload, the activation
+ *       parameters follow the header; r = Jcom(q) (v+ - v), nr = 3
+ *     On an impulse knot (FDDP_KNOT_IMPULSEFWD) the records 7, 9 and 11 are
+ *     CostModelContactImpulse, CostModelImpulseFrictionCone and
+ *     CostModelImpulseCoPPosition: the same payloads, row0 indexing the stacked
+ *     impulse rows, lambda the impulse's multipliers Lambda.
  * At most 64 dofs, 64 cost records and 64 stacked residual rows with dense
  * Jacobians per knot (the calcDiff LDS plan must fit; fddp_create says why not). */
 #define FDDP_KNOT_EULER_FREEFWD 4
@@ -135,13 +141,20 @@ int fddp_abi_version(void);
  * action model (no integrator), nu = 0, xnext = (q, v+) with the impulse
  * dynamics [M Jc^T; Jc 0][v+; -Lambda] = [M v; -r_coeff Jc v], cost = costs(x);
  * ImpulseModelMultiple of ImpulseModel3D / 6D (impulses/impulse-{3d,6d}.hxx).
- * Block: the FDDP_KNOT_EULER_FREEFWD layout with dt = 0 (no frame-velocity or
- * force costs), then
- *   [r_coeff, JMinvJt_damping, nimpulse, 1]
+ * Block: the FDDP_KNOT_EULER_FREEFWD layout with dt = 0 (no frame-velocity
+ * costs; the cost records 7, 9, 11 read the impulses' multipliers, 13 the CoM
+ * velocity change), then
+ *   [r_coeff, JMinvJt_damping, nimpulse, flag (1; 3 = enable_force: the
+ *    multiplier Jacobians the records 7, 9, 11 read)]
  *   nimpulse active impulse records in name order, each
  *     [type (5: 3D, 6: 6D), 0, 0, size = 17], frame joint, frame placement R(9) p(3)
  * calcDiff follows the reference's formula (restitution terms left out of Fx, as
- * impulse-fwddyn.hxx:111-115). At most 24 stacked impulse rows. */
+ * impulse-fwddyn.hxx:111-115). With flag 3,
+ *   d Lambda / dx = [H^T dtau_dq - S^-1 dv0_dq, -S^-1 Jc]
+ * (S = Jc M^-1 Jc^T + damping I, H = M^-1 Jc^T S^-1; q and v columns, no u): the
+ * exact derivative at r_coeff = 0, the restitution terms left out otherwise, as in
+ * Fx; with flag 1 the Jacobians of 7, 9, 11 are zero. Record 13 does not depend on
+ * the flag. At most 24 stacked impulse rows. */
 #define FDDP_KNOT_IMPULSEFWD 6
 
 #define FDDP_PARAM_HEADER 4 /* doubles of scalar header in front of every block */
