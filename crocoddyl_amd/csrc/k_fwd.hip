@@ -8,6 +8,8 @@
 // 256-VGPR cap), and measured on the C5 walk out of line its calls cost the rollout 6 %
 // (29.9 -> 31.8 ms per step), more than the solve gains.
 #define MB_CALC_DENSE 1
+// the centroidal-momentum record's evaluation is a call here (mb_costs.hpp)
+#define MB_MOMENTUM_OUTLINE 1
 // the multibody-only variants keep the knot's parsed block header in scalar registers
 // (multibody.hpp MB_BLK_UNIFORM) and give every phase of the calc a fresh copy of its lane
 // index (MB_LANE_OPAQUE)
@@ -19,6 +21,9 @@
 // (launch_plan.hpp plan_variants), so its calc is built without that cost's phases
 #if defined(FDDP_TU_FWD) && FDDP_TU_FWD == 1
 #define MB_CALC_IMPULSE_COM 0
+// ... nor one with a CostModelCentroidalMomentum record (at its register cap the record's
+// evaluation costs it 23 more VGPR spills on every horizon)
+#define MB_CALC_MOMENTUM 0
 #endif
 #include "fast_path.hpp"
 #include "fddp_kernels.hpp"

@@ -59,6 +59,7 @@ struct LdsPlan {
   bool has_mb = false;          // multibody knots present (mb_knot_kernel)
   bool all_mb = false;          // every knot is a multibody knot
   bool has_icom = false;        // a knot carries a CostModelImpulseCoM record (no FWD_MB rollout)
+  bool has_hmom = false;        // a knot carries a CostModelCentroidalMomentum record (no FWD_MB rollout)
   int mb_nj = 0;                // largest multibody tree (dofs)
   int64_t mbw = 0, mbw_fwd = 0, mbd = 0;  // Dev::mbw, mbw_fwd, mbd
   int mbspill = 0, dxv_mbw = 0;           // Dev::mbspill, dxv_mbw
@@ -176,6 +177,10 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
       if (!impulse) return why = "the impulse CoM cost needs an impulse knot", -1;
       want = kCHdr + ap * 3;
     }
+    if (type == C_CENTROIDAL_MOMENTUM) {  // [href(6)]; an impulse knot runs no kinematics at v
+      if (impulse) return why = "centroidal-momentum costs are covered on Euler knots only", -1;
+      want = kCHdr + 6 + ap * 6;
+    }
     if (type == C_CONTACT_FORCE || type == C_FRICTION_CONE || type == C_COP_POSITION) {
       // [row0, nr, fref(6)] | [row0, nc, nr, A(3 nr)] | [row0, nc, nr, A(6 nr)]; rows checked against the
       // contacts below (on an impulse knot: against its impulses, whose multipliers the rows index)
@@ -215,9 +220,10 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
       for (int e = 0; e < 7; ++e)
         if (!std::isfinite(C[kCHdr + e])) return why = "non-finite reference state", -1;
     if (type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_COM_POSITION ||
-        type == C_FRAME_VELOCITY || type == C_FRAME_ROTATION || type == C_IMPULSE_COM || (type == C_STATE && ff))
+        type == C_FRAME_VELOCITY || type == C_FRAME_ROTATION || type == C_IMPULSE_COM ||
+        type == C_CENTROIDAL_MOMENTUM || (type == C_STATE && ff))
       ++njac;
-    if (type == C_FRAME_VELOCITY) vcols = true;
+    if (type == C_FRAME_VELOCITY || type == C_CENTROIDAL_MOMENTUM) vcols = true;
     o += rs;
   }
   int nc = 0;
@@ -327,6 +333,7 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
                                           &k.njac, &k.nc, &k.vcols, &k.nu, &k.nrows);
         if (s1 < 0 && !refused) refused = why.text;
         if (s1 >= 0 && fddp::mb::has_impulse_com(fddp::mb::parse(params + off))) p.has_icom = true;
+        if (s1 >= 0 && fddp::mb::has_momentum(fddp::mb::parse(params + off))) p.has_hmom = true;
         // (a refused block is planned with its size field, as mb_pmax is: the budget below
         // then refuses only what is over it)
         const int64_t own = (int64_t)params[off + 3];
@@ -410,6 +417,8 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
   if (refused) p.error = refused;
   if (!p.error && p.has_icom && ov.fwd_mbw == 3)
     p.error = "FDDP_FWD_MBW=3 on a horizon with an impulse CoM cost: that rollout build does not evaluate it";
+  if (!p.error && p.has_hmom && ov.fwd_mbw == 3)
+    p.error = "FDDP_FWD_MBW=3 on a horizon with a centroidal-momentum cost: that rollout build does not evaluate it";
   return p;
 }
 
@@ -449,9 +458,10 @@ inline VariantPlan plan_variants(const LdsPlan& l, const fddp_dims& d, const Ove
     v.fwd = ktab::FWD_GENERIC;
   } else {
     const bool three = resident_per_cu(f.fwd_api[ktab::FWD_MB], l.fwd_smem, f.fwd_static[ktab::FWD_MB]) >= 3;
-    // (a horizon with an impulse CoM cost never: that build's calc has no code for it,
-    // MB_CALC_IMPULSE_COM; plan_lds refuses the override that would force it)
-    const bool take3 = !l.has_icom && (ov.fwd_mbw ? ov.fwd_mbw == 3 : (three && d.B > 2 * cus));
+    // (a horizon with an impulse CoM or a centroidal-momentum cost never: that build's calc has
+    // no code for them, MB_CALC_IMPULSE_COM / MB_CALC_MOMENTUM; plan_lds refuses the override
+    // that would force it)
+    const bool take3 = !l.has_icom && !l.has_hmom && (ov.fwd_mbw ? ov.fwd_mbw == 3 : (three && d.B > 2 * cus));
     v.fwd = take3 ? ktab::FWD_MB : ktab::FWD_MB2;
   }
   if (!l.fast) v.ls_slots = (double)cus * resident_per_cu(f.fwd_api[v.fwd], l.fwd_smem, f.fwd_static[v.fwd]);

@@ -102,6 +102,13 @@ MB_HD __forceinline__ T* mb_lds(T* p) {
 #ifndef MB_CALC_IMPULSE_COM
 #define MB_CALC_IMPULSE_COM 1
 #endif
+// MB_CALC_MOMENTUM (per kernel object): the rollout's calc evaluates CostModelCentroidalMomentum
+// records (with the other records, beside the CRBA composites). As MB_CALC_IMPULSE_COM: the
+// three-waves-per-EU rollout object is built without it, and the launch plan never gives it a
+// horizon with such a record (LdsPlan::has_hmom, plan_variants).
+#ifndef MB_CALC_MOMENTUM
+#define MB_CALC_MOMENTUM 1
+#endif
 
 namespace fddp {
 namespace mb {
@@ -110,7 +117,7 @@ typedef unsigned long long Mask;  // one bit per dof
 constexpr int kMaxJ = 64;         // dofs (nv)
 constexpr int kJRec = 27;         // doubles per joint record
 constexpr int kCHdr = 4;          // doubles of a cost record's header
-constexpr int kMaxJacCosts = 8;   // costs with a dense residual Jacobian (frame, CoM, impulse CoM, free-flyer state)
+constexpr int kMaxJacCosts = 8;   // costs with a dense residual Jacobian (frame, CoM, impulse CoM, momentum, free-flyer state)
 constexpr int kMaxNc = 24;        // stacked contact rows (FDDP_KNOT_EULER_CONTACTFWD)
 constexpr int kMbDiffNT = 256;    // threads of the knot-parallel calcDiff workgroup
 enum { J_REVOLUTE = 0, J_FREEFLYER = 1 };
@@ -133,7 +140,9 @@ enum {
   C_COP_POSITION = 11,    // r = A lambda of a 6D contact: payload [row0, nc, nr, A (nr x 6 row-major)]
                           // (contact-cop-position.hpp)
   C_FRAME_ROTATION = 12,  // r = log3(Rref^T oRf): frame payload + Rref^T (9) (frame-rotation.hxx)
-  C_IMPULSE_COM = 13      // r = Jcom(q) (v+ - v) on an impulse knot: empty payload (CostModelImpulseCoM)
+  C_IMPULSE_COM = 13,     // r = Jcom(q) (v+ - v) on an impulse knot: empty payload (CostModelImpulseCoM)
+  C_CENTROIDAL_MOMENTUM = 14  // r = hg(q, v) - href, hg = [linear; angular about the CoM], world axes: payload
+                              // [href(6)] (centroidal-momentum.hxx); Euler knots only
 };
 // Activation of a cost record: header slot 2 (core/activations/*.hpp)
 enum { A_QUAD = 0, A_WEIGHTED_QUAD = 1, A_QUAD_BARRIER = 2, A_WEIGHTED_QUAD_BARRIER = 3 };

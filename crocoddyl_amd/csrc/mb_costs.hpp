@@ -93,7 +93,7 @@ MB_HD inline int cost_nr(const Blk& b, const CRec& C, int nu) {
   if (t == C_FRICTION_CONE || t == C_COP_POSITION) return (int)C.d()[2];
   if (t == C_STATE) return 2 * b.nj;
   if (t == C_CONTROL) return nu;
-  return (t == C_FRAME_PLACEMENT || t == C_FRAME_VELOCITY) ? 6 : 3;
+  return (t == C_FRAME_PLACEMENT || t == C_FRAME_VELOCITY || t == C_CENTROIDAL_MOMENTUM) ? 6 : 3;
 }
 // The activation of a cost record (its parameters end the record):
 //   Quad / WeightedQuad (quadratic.hpp, weighted-quadratic.hpp:42-71): w (ones if
@@ -134,12 +134,14 @@ MB_HD inline Act cost_act(const Blk& b, const CRec& C, int nu) {
 }
 // costs whose residual Jacobian is dense over the configuration tangent (stored
 // per cost: rows x jw, jw = nj, or 2 nj when a frame-velocity cost needs the
-// velocity columns too): frame costs, CoM, frame velocity, the free-flyer block of a
-// state cost, and the impulse CoM cost (its slot holds d(Jcom w)/dq and Jcom, three rows each:
-// the rows of R are formed from them and Fx, knot_calc_diff_x)
+// velocity columns too; so does a centroidal-momentum cost): frame costs, CoM, frame velocity,
+// centroidal momentum, the free-flyer block of a state cost, and the impulse CoM cost (its slot
+// holds d(Jcom w)/dq and Jcom, three rows each: the rows of R are formed from them and Fx,
+// knot_calc_diff_x)
 MB_HD __forceinline__ bool jac_cost(const Blk& b, int type) {
   return type == C_FRAME_PLACEMENT || type == C_FRAME_TRANSLATION || type == C_COM_POSITION ||
-         type == C_FRAME_VELOCITY || type == C_FRAME_ROTATION || type == C_IMPULSE_COM || (type == C_STATE && b.ff);
+         type == C_FRAME_VELOCITY || type == C_FRAME_ROTATION || type == C_IMPULSE_COM ||
+         type == C_CENTROIDAL_MOMENTUM || (type == C_STATE && b.ff);
 }
 MB_HD __forceinline__ int jac_rows(int type) {
   const bool three =
@@ -153,7 +155,7 @@ MB_HD inline int count_jac_costs(const Blk& b, bool* vel_cols = nullptr) {
   for (int k = 0; k < b.ncost; ++k) {
     const CRec C{cr};
     if (jac_cost(b, C.type())) ++n;
-    if (C.type() == C_FRAME_VELOCITY) fv = true;
+    if (C.type() == C_FRAME_VELOCITY || C.type() == C_CENTROIDAL_MOMENTUM) fv = true;
     cr += C.size();
   }
   if (vel_cols) *vel_cols = fv;
@@ -262,6 +264,38 @@ MB_HD inline void com_value(const Blk& b, const WVals& W, double* c) {
   for (int e = 0; e < 3; ++e) c[e] = h[e] / m;
 }
 
+// ---- CostModelCentroidalMomentum: r = hg(q, v) - href -----------------------------------
+// The momentum about the world origin of the bodies below dof j (j < 0: of every body),
+// h = sum I_b v_b, from the bodies' world velocities (W.v: after the velocity pass) and their
+// mass, CoM and inertia in the D records.
+MB_HD inline void subtree_momentum(const Blk& b, const WVals& W, int j, double* h) {
+  for (int e = 0; e < 6; ++e) h[e] = 0.;
+  for (int k = 0; k < b.nj; ++k) {
+    if (!carries_body(b, k)) continue;
+    if (j >= 0 && !((*W.anc(k) >> j) & 1ull)) continue;
+    const double mk = *W.m(k);
+    double c[3], I6[6], V[6], f[6];
+    for (int e = 0; e < 3; ++e) c[e] = W.c(k)[e];
+    for (int e = 0; e < 6; ++e) {
+      I6[e] = W.Ic(k)[e];
+      V[e] = W.v(k)[e];
+    }
+    inertia_mul(mk, c, I6, V, f);
+    for (int e = 0; e < 6; ++e) h[e] += f[e];
+  }
+}
+// hg of pinocchio::computeCentroidalMomentum: [l; k_O - c x l], world axes, about the CoM c
+MB_HD inline void centroidal_momentum(const Blk& b, const WVals& W, double* hg) {
+  double h[6], c[3], t[3];
+  subtree_momentum(b, W, -1, h);
+  com_value(b, W, c);
+  cross3(c, h, t);
+  for (int e = 0; e < 3; ++e) {
+    hg[e] = h[e];
+    hg[3 + e] = h[3 + e] - t[e];
+  }
+}
+
 // ---- CostModelImpulseCoM: r = Jcom(q) (v+ - v), the change of the CoM velocity ----------
 // lane i < nj: the mass of dof i's body times the velocity of its CoM under the generalised
 // velocity w (wq(k): its entry k), o[0..2]; from the L records (oMi, S) and the block alone,
@@ -349,6 +383,36 @@ MB_HD MB_NOINLINE_DEV void impulse_com_calc_value(const Blk& b, const WVals& W, 
   for (int e = 0; e < 3; ++e) a += act.value2(e, r[e]);
   cv[kf] = C.weight() * (0.5 * a);
 }
+// The calc's value of a centroidal-momentum record: twice its activation. Out of line in the
+// rollout's objects for the same reason (MB_MOMENTUM_OUTLINE, k_fwd.hip); inlined in the
+// others, where a call would cost the calcDiff kernels spills around it.
+#ifndef MB_MOMENTUM_OUTLINE
+#define MB_MOMENTUM_OUTLINE 0
+#endif
+#if MB_MOMENTUM_OUTLINE
+#define MB_MOMENTUM_INLINE MB_NOINLINE_DEV
+#else
+#define MB_MOMENTUM_INLINE inline
+#endif
+MB_HD MB_MOMENTUM_INLINE double momentum_calc_value2(const Blk& b, const WVals& W, const CRec& C) {
+  double r[6];
+  centroidal_momentum(b, W, r);
+  const Act act = cost_act(b, C, 0);
+  double a = 0.;
+  for (int i = 0; i < 6; ++i) a += act.value2(i, r[i] - C.d()[i]);
+  return a;
+}
+// whether the block has a centroidal-momentum cost
+MB_HD inline bool has_momentum(const Blk& b) {
+  bool found = false;
+  const double* cr = b.C;
+  for (int k = 0; k < b.ncost; ++k) {
+    const CRec C{cr};
+    found = found || C.type() == C_CENTROIDAL_MOMENTUM;
+    cr += C.size();
+  }
+  return found;
+}
 
 // free-flyer block of a state residual: log6(Mref^-1 M) (multibody.hxx:69)
 MB_HD inline void ff_rel(const double* xref, const double* x, double* Rr, double* pr) {
@@ -378,8 +442,8 @@ MB_HD inline void frame_velocity_res(const Blk& b, const WVals& V, const double*
 }
 
 // Activation value of one cost record (kinematics in V; velocities in V only with
-// vel: frame-velocity costs are skipped without). Force costs and the impulse CoM cost
-// return 0: they need the multipliers / v+ and are added after the contact solve.
+// vel: frame-velocity and centroidal-momentum costs are skipped without). Force costs and the
+// impulse CoM cost return 0: they need the multipliers / v+ and are added after the contact solve.
 MB_HD __forceinline__ double cost_activation(const Blk& b, const WVals& V, const CRec& C, const double* x,
                                              const double* u, int nu, bool vel = true) {
   const Act act = cost_act(b, C, nu);
@@ -408,6 +472,11 @@ MB_HD __forceinline__ double cost_activation(const Blk& b, const WVals& V, const
     double r[6];
     frame_velocity_res(b, V, C.d(), r);
     for (int i = 0; i < 6; ++i) a += act.value2(i, r[i]);
+#if MB_CALC_MOMENTUM
+  } else if (C.type() == C_CENTROIDAL_MOMENTUM) {
+    if (!vel) return 0.;
+    a = momentum_calc_value2(b, V, C);
+#endif
   } else {
     double r[6] = {0., 0., 0., 0., 0., 0.};
     const int nr = frame_residual_value(b, V, C, r);

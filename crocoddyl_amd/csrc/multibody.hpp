@@ -701,7 +701,8 @@ MB_HD __forceinline__ void calc_cost_records(const double* P_, double* w_, doubl
       ++nw;
     } else {
       if (item == nn) {
-        double v = C.type() == C_FRAME_VELOCITY && imp ? 0. : cost_activation(b, W, C, x, ub, nu);
+        const bool vc = C.type() == C_FRAME_VELOCITY || C.type() == C_CENTROIDAL_MOMENTUM;
+        double v = vc && imp ? 0. : cost_activation(b, W, C, x, ub, nu);
         if (force_cost(C.type()) && nc == 0) v = force_cost_activation(b, C, nullptr, nu);
         cv[k] = C.weight() * v;
       }
@@ -1691,8 +1692,75 @@ MB_HD inline void impulse_direction(const Blk& b, const WVals& W, int j, int L, 
   }
 }
 
-// lane j < nj: column j of every jac-cost Jacobian (Jf[(f*6 + e)*jw + j]; a
-// frame-velocity cost also its velocity column nj + j) and, on lane 0, their
+// Column j of the centroidal momentum's two Jacobian halves (CostModelCentroidalMomentum):
+// Jq = dhg/dq_j, Jv = column j of Ag. About the world origin, with h_sub(j) the momentum of
+// the bodies below dof j, Y_j their composite inertia and V_P the parent body's velocity
+// (turning q_j moves the subtree rigidly by S_j and changes its velocities by V_P x S_j; the
+// free-flyer's dofs have V_P = 0, as for the frame-velocity cost):
+//   dh_O/dv_j = Y_j S_j,   dh_O/dq_j = S_j x* h_sub(j) + Y_j (V_P x S_j).
+// Moved to the CoM c, l the linear momentum: k = k_O - c x l, so
+//   dk/dq_j = dk_O/dq_j - Jcom_j x l - c x dl/dq_j,   dk/dv_j = dk_O/dv_j - c x dl/dv_j.
+// One pass over the bodies gives h_sub(j), the total momentum, the mass and the CoM; the
+// columns are stored as they are formed (Jq[e * ld], Jv[e * ld]), the velocity column first,
+// so that few values are live at once. href != null (lane 0): the residual into r as well.
+MB_HD inline void momentum_columns(const Blk& b, const WVals& W, int j, double* Jq, double* Jv, int64_t ld,
+                                   const double* href, double* r) {
+  double hs[6] = {0., 0., 0., 0., 0., 0.}, ht[6] = {0., 0., 0., 0., 0., 0.}, c[3] = {0., 0., 0.}, mt = 0.;
+  for (int k = 0; k < b.nj; ++k) {
+    if (!carries_body(b, k)) continue;
+    const double mk = *W.m(k);
+    const double sel = ((*W.anc(k) >> j) & 1ull) ? 1. : 0.;
+    double ck[3], I6[6], V[6], f[6];
+    for (int e = 0; e < 3; ++e) ck[e] = W.c(k)[e];
+    for (int e = 0; e < 6; ++e) {
+      I6[e] = W.Ic(k)[e];
+      V[e] = W.v(k)[e];
+    }
+    inertia_mul(mk, ck, I6, V, f);
+    mt += mk;
+    for (int e = 0; e < 3; ++e) c[e] += mk * ck[e];
+    for (int e = 0; e < 6; ++e) {
+      ht[e] += f[e];
+      hs[e] += sel * f[e];
+    }
+  }
+  for (int e = 0; e < 3; ++e) c[e] /= mt;
+  if (href) {  // hg = [l; k_O - c x l]
+    double t[3];
+    cross3(c, ht, t);
+    for (int e = 0; e < 3; ++e) {
+      r[e] = ht[e] - href[e];
+      r[3 + e] = ht[3 + e] - t[e] - href[3 + e];
+    }
+  }
+  double S[6], d6[6], t3[3];
+  for (int e = 0; e < 6; ++e) S[e] = W.S(j)[e];
+  comp_mul(W, j, S, d6);  // dh_O/dv_j
+  cross3(c, d6, t3);
+  for (int e = 0; e < 3; ++e) {
+    Jv[e * ld] = d6[e];
+    Jv[(3 + e) * ld] = d6[3 + e] - t3[e];
+  }
+  double VP[6], AP[6], u6[6], t6[6];
+  parent_motion(b, W, j, VP, AP);
+  cross_m(VP, S, u6);
+  comp_mul(W, j, u6, d6);
+  cross_f(S, hs, t6);
+  for (int e = 0; e < 6; ++e) d6[e] += t6[e];  // dh_O/dq_j
+  double jc[3], a1[3];
+  cross3(S + 3, W.ch(j), t3);  // Jcom col j = (m_sub S_lin + S_ang x h_sub) / m_total
+  const double m = *W.cm(j);
+  for (int e = 0; e < 3; ++e) jc[e] = (m * S[e] + t3[e]) / mt;
+  cross3(jc, ht, a1);
+  cross3(c, d6, t3);
+  for (int e = 0; e < 3; ++e) {
+    Jq[e * ld] = d6[e];
+    Jq[(3 + e) * ld] = d6[3 + e] - a1[e] - t3[e];
+  }
+}
+
+// lane j < nj: column j of every jac-cost Jacobian (Jf[(f*6 + e)*jw + j]; a frame-velocity
+// or centroidal-momentum cost also its velocity column nj + j) and, on lane 0, their
 // residuals (rf[6 f + e]); lanes j < 6 of a free-flyer knot also the Euler step's
 // Jexp6(dq) column j (Je, col-major 6x6) and, on lane 0, Ad(exp6(dq)^-1) (Ai).
 // only: -1 every jac cost, -2 none (the free-flyer Euler terms alone), f >= 0 jac cost f
@@ -1731,6 +1799,11 @@ MB_HD inline void jac_lane(const Blk& b, const WVals& W, const double* x, int j,
         }
         for (int e = 0; e < 6; ++e) Jf[((int64_t)f * 6 + e) * jw + nj + j] = Jv[e];
         if (j == 0) frame_velocity_res(b, W, d, r);
+      } else if (t == C_CENTROIDAL_MOMENTUM) {  // [dhg/dq_j, Ag_j]
+        // (the q column stored here, and once more by the common store below)
+        double* Jq = Jf + (int64_t)f * 6 * jw + j;
+        momentum_columns(b, W, j, Jq, Jq + nj, jw, j == 0 ? C.d() : nullptr, r);
+        for (int e = 0; e < 6; ++e) Jc[e] = Jq[(int64_t)e * jw];
       } else if (t == C_COM_POSITION) {  // Jcom col j = (m_sub S_lin + S_ang x h_sub) / m_total
         double mt = 0.;
         for (int bb = 0; bb < nj; ++bb)
@@ -2729,7 +2802,8 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
           cg[4 * g] = r0;
           cg[4 * g + 1] = row;
           cg[4 * g + 2] = co;
-          cg[4 * g + 3] = t == C_FRAME_VELOCITY ? 1. : 0.;  // 0: q columns only, 1: x columns
+          // 0: q columns only, 1: x columns
+          cg[4 * g + 3] = (t == C_FRAME_VELOCITY || t == C_CENTROIDAL_MOMENTUM) ? 1. : 0.;
           ++g;
           ++f;
         }

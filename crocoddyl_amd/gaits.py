@@ -53,10 +53,13 @@ class SimpleBipedGaitProblem:
     ``impulseCosts``: createImpulseModel adds a CostModelImpulseFrictionCone (1e1) on every
     support foot and, with ``copSupport``, a CostModelImpulseCoPPosition (``copWeight``), and
     computes the multiplier Jacobians they read (enable_force). ``pseudoImpulse``: what the
-    foot switches of the walking gait are (biped.py:218-229 takes the pseudo-impulse)."""
+    foot switches of the walking gait are (biped.py:218-229 takes the pseudo-impulse).
+    ``momentumWeight``: every swing-foot and flying model gets a CostModelCentroidalMomentum
+    with href = 0 and a WeightedQuad activation on the angular half, (0, 0, 0, 1, 1, 1), at
+    that weight: an angular-momentum regulariser; None: no such cost."""
 
     def __init__(self, rmodel, rightFoot, leftFoot, copSupport=None, copWeight=1e1, impulseCosts=False,
-                 pseudoImpulse=True):
+                 pseudoImpulse=True, momentumWeight=None):
         self.rmodel = rmodel
         self.state = mb.StateMultibody(self.rmodel)
         self.actuation = mb.ActuationModelFloatingBase(self.state)
@@ -71,6 +74,7 @@ class SimpleBipedGaitProblem:
         self.copWeight = float(copWeight)
         self.impulseCosts = bool(impulseCosts)
         self.pseudoImpulse = bool(pseudoImpulse)
+        self.momentumWeight = None if momentumWeight is None else float(momentumWeight)
 
     def createWalkingModels(self, x0, stepLength, stepHeight, timeStep, stepKnots, supportKnots):
         """The running models of createWalkingProblem (biped.py:25-65)."""
@@ -206,6 +210,11 @@ class SimpleBipedGaitProblem:
         stateWeights = np.array([0] * 3 + [500.] * 3 + [0.01] * (self.state.nv - 6) + [10] * self.state.nv)
         costModel.addCost("stateReg", self._stateReg(stateWeights, self.actuation.nu), 1e1)
         costModel.addCost("ctrlReg", mb.CostModelControl(self.state, self.actuation.nu), 1e-1)
+        if self.momentumWeight is not None:
+            hReg = mb.CostModelCentroidalMomentum(
+                self.state, mb.ActivationModelWeightedQuad(np.array([0., 0., 0., 1., 1., 1.])), np.zeros(6),
+                self.actuation.nu)
+            costModel.addCost("momentumReg", hReg, self.momentumWeight)
         dmodel = mb.DifferentialActionModelContactFwdDynamics(self.state, self.actuation, contactModel, costModel,
                                                               0., True)
         return IntegratedActionModelEuler(dmodel, timeStep)

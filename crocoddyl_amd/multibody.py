@@ -43,6 +43,7 @@ COST_FRAME_VELOCITY = 10
 COST_COP_POSITION = 11
 COST_FRAME_ROTATION = 12
 COST_IMPULSE_COM = 13
+COST_CENTROIDAL_MOMENTUM = 14
 MAX_CONTACT_ROWS = 24
 MAX_DOFS = 64  # nv of the device path (one lane per tangent direction of a wave pair)
 
@@ -1244,6 +1245,30 @@ class CostModelFrameVelocity(_Cost):
         return [frame, self.vref.motion.vector.reshape(1, -1)]
 
 
+class CostModelCentroidalMomentum(_Cost):
+    """r = hg(q, v) - href (centroidal-momentum.hxx): hg is the centroidal momentum of
+    pinocchio::computeCentroidalMomentum, [linear; angular about the CoM] in world axes;
+    Rx = [dhg/dq, Ag], Ru = 0. Overloads (state, activation, href[, nu]) and
+    (state, href[, nu]) with ActivationModelQuad(6) by default. Record type 14, payload
+    href(6); valid on Euler knots only (an impulse knot runs no kinematics at v). Parity
+    unpinned against the reference binary."""
+
+    type = COST_CENTROIDAL_MOMENTUM
+
+    def __init__(self, state, *args, **kw):
+        act, ref, nu = _cost_args(args, kw)
+        ref = kw.get("href", ref)
+        if ref is None:
+            raise TypeError("CostModelCentroidalMomentum needs a reference momentum href")
+        super().__init__(state, act, 6, nu)
+        self.href = np.array(ref, np.float64)
+        if self.href.shape[-1] != 6:
+            raise ValueError("Invalid argument: href has wrong dimension (it should be 6)")
+
+    def _payload(self):
+        return [_rows(self.href, 6)]
+
+
 class CostItem:
     """CostItem (cost-sum.hpp): name, cost, weight, active; changing the weight
     marks the owning CostModelSum as modified (its blocks are re-packed)."""
@@ -1772,7 +1797,10 @@ class ActionModelImpulseFwdDynamics(_impulse_model_base()):
     def pack(self):
         recs = self.impulses.pack()
         # the contact classes read a contact's data collector, which an impulse knot has not
-        # (their Impulse* twins read the impulses'); frame velocities are not covered here
+        # (their Impulse* twins read the impulses'); frame velocities and the centroidal momentum
+        # are not covered here (an impulse knot runs no kinematics at v)
+        if any(it.active and it.cost.type == COST_CENTROIDAL_MOMENTUM for it in self.costs.costs.values()):
+            raise NotImplementedError("crocoddyl_amd: centroidal-momentum costs on impulse knots are not covered")
         if any(it.active and (it.cost.type == COST_FRAME_VELOCITY or
                               (it.cost.type in _FORCE_COSTS and not getattr(it.cost, "impulse_cost", False)))
                for it in self.costs.costs.values()):

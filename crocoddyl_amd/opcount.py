@@ -35,6 +35,10 @@ Impulse knots (impulse-fwddyn.hxx) take the calc's and calcDiff's contact terms 
 the impulse rows; free-dynamics knots nc = 0. The impulse costs: the multiplier rows as
 the contact costs' (over the x columns), CostModelImpulseCoM 10 n for Jcom (v+ - v) and,
 in calcDiff, Jcom, d(Jcom w)/dq and Jcom times the bottom rows of Fx.
+CostModelCentroidalMomentum: hg 88 n (I v per body, moved to the origin, the CoM); in
+calcDiff dhg/dq and Ag at 186 n (per dof Y S, Y (v x S), S x* h_sub, the shift to the CoM) and
+the Gauss-Newton products over the x columns. Its bytes are the record's, counted with the
+block.
 
 These are estimates of the reference's arithmetic, stated so that the roofline's
 flop fraction can be reproduced; bench.py reports them beside the HBM roofline and
@@ -107,6 +111,13 @@ def _cost_terms(dam, n, nu, L, robot, par):
             # bottom rows of Fx (3 x n x L), Gauss-Newton over the x columns
             calc += 10 * n
             diff += 10 * n * 3 + 3 * C_CR * n + 2 * 3 * n * L + nr * L * (L + 1) + 2 * nr * L
+        elif isinstance(c, mb.CostModelCentroidalMomentum):
+            # hg: per body I v and its transform to the origin, the CoM, the shift to it; dhg/dq
+            # and Ag (computeCentroidalDynamicsDerivatives): per dof Y S, Y (v x S), S x* h_sub
+            # and the shift to the CoM, per body the backward transform of its momentum;
+            # Gauss-Newton over the x columns
+            calc += (C_I + C_X) * n + 10 * n + C_CR
+            diff += (2 * C_I + 3 * C_CR + C_X) * n + 10 * n * 3 + nr * L * (L + 1) + 2 * nr * L
         elif isinstance(c, mb.CostModelState):
             calc += 2 * L + (100 if robot.has_freeflyer else 0)
             diff += 4 * L + (72 * 6 if robot.has_freeflyer else 0)

@@ -36,7 +36,7 @@ CONFIGS = {
 }
 
 
-def gait_models(name, T=None, copSupport=None, impulseCosts=False, pseudoImpulse=True):
+def gait_models(name, T=None, copSupport=None, impulseCosts=False, pseudoImpulse=True, momentumWeight=None):
     """(gait builder, running models, terminal model) of a gait config. The knot
     counts are the reference benchmark's gait parameters stretched to the config's
     T: Talos walking (benchmark/bipedal_walk_optctrl.py:82-90: step 0.6 m / 0.1 m,
@@ -45,13 +45,15 @@ def gait_models(name, T=None, copSupport=None, impulseCosts=False, pseudoImpulse
     2 support knots) with 27 step knots -> T = 60. A smaller T shortens the steps
     (for parity tests). ``copSupport`` = (L, W): the biped's feet get a
     CostModelContactCoPPosition each (gaits.SimpleBipedGaitProblem); ``impulseCosts`` /
-    ``pseudoImpulse``: the biped's foot switches as impulse knots with their impulse costs."""
+    ``pseudoImpulse``: the biped's foot switches as impulse knots with their impulse costs;
+    ``momentumWeight``: the biped's angular-momentum regulariser (CostModelCentroidalMomentum)."""
     from . import gaits, robots
     kind, _, _, T0, _, dt = CONFIGS[name]
     T = T0 if T is None else T
     if kind == "gait_biped":
         g = gaits.SimpleBipedGaitProblem(robots.sample_talos(), "right_sole_link", "left_sole_link",
-                                         copSupport=copSupport, impulseCosts=impulseCosts, pseudoImpulse=pseudoImpulse)
+                                         copSupport=copSupport, impulseCosts=impulseCosts, pseudoImpulse=pseudoImpulse,
+                                         momentumWeight=momentumWeight)
         sk = max(1, T // 2 - 2)
         models = g.createWalkingModels(g.rmodel.defaultState, 0.6, 0.1, dt, sk, 1)
     else:
@@ -63,12 +65,12 @@ def gait_models(name, T=None, copSupport=None, impulseCosts=False, pseudoImpulse
 
 
 def build_gait(name, T=None, B=None, seed=None, spread=0.02, v_spread=0.1, copSupport=None, impulseCosts=False,
-               pseudoImpulse=True):
+               pseudoImpulse=True, momentumWeight=None):
     """(x0s, running, terminal) of a gait config: x0_b = the reference posture
     integrated along a seeded tangent perturbation (q +- spread, v +- v_spread)."""
     _, _, _, T0, B0, _ = CONFIGS[name]
     B = B0 if B is None else B
-    g, running, terminal = gait_models(name, T, copSupport, impulseCosts, pseudoImpulse)
+    g, running, terminal = gait_models(name, T, copSupport, impulseCosts, pseudoImpulse, momentumWeight)
     rng = np.random.default_rng(seed_of(name) + 1 if seed is None else seed)
     x0 = g.rmodel.defaultState
     nv = g.state.nv
@@ -196,7 +198,7 @@ def build_hetero(name, T=None, B=None, seed=None, phase=10, impulse_every=7):
 
 def build_arm_contact(T=4, B=2, seed=0, robot=None, dt=1e-2, contact="6d", gains=(2.0, 1.5), damping=0.0,
                       weighted=False, armature=None, inactive=False, q_nominal=None, spread=1.0, force_costs=False,
-                      enable_force=None, cop=None, cop_weights=None, cop_inactive=False, frot=False):
+                      enable_force=None, cop=None, cop_weights=None, cop_inactive=False, frot=False, hmom=None):
     """Contact-dynamics knots on the arm: Euler(dt) ∘ DifferentialActionModelContactFwdDynamics
     (contact-fwddyn.hxx) with ActuationModelFloatingBase (first joint unactuated)
     and a ContactModelMultiple on the gripper frame ("6d": ContactModel6D, "3d":
@@ -212,7 +214,8 @@ def build_arm_contact(T=4, B=2, seed=0, robot=None, dt=1e-2, contact="6d", gains
     adds a CostModelContactCoPPosition on the gripper's 6D contact (QuadraticBarrier,
     or WeightedQuadraticBarrier with the four ``cop_weights``; with ``cop_inactive``
     also on a switched-off 6D contact of the elbow frame); ``frot`` a
-    CostModelFrameRotation on the elbow frame."""
+    CostModelFrameRotation on the elbow frame; ``hmom`` a CostModelCentroidalMomentum with the
+    activation it names ("quad", "wquad", "barrier", "wbarrier")."""
     from . import multibody as mb
     rng = np.random.default_rng(seed)
     model = mb.sample_talos_arm() if robot is None else robot
@@ -260,6 +263,8 @@ def build_arm_contact(T=4, B=2, seed=0, robot=None, dt=1e-2, contact="6d", gains
             costs.addCost("auxCoP", _cop_cost(mb, state, eid, cop, cop_weights, nu), 0.2)
     if frot:
         costs.addCost("elbowRot", mb.CostModelFrameRotation(state, mb.FrameRotation(eid, _frot_ref(mb)), nu), 0.4)
+    if hmom is not None:
+        costs.addCost("hMom", _hmom_cost(mb, state, hmom, nu), 0.3)
     dam = mb.DifferentialActionModelContactFwdDynamics(
         state, act, contacts, costs, damping,
         (force_costs or cop is not None) if enable_force is None else enable_force)
@@ -283,6 +288,16 @@ def _cop_cost(mb, state, fid, box, weights, nu):
         return mb.CostModelContactCoPPosition(state, sup, nu)
     bounds = mb.ActivationBounds(np.zeros(4), np.full(4, mb.DBL_MAX))
     return mb.CostModelContactCoPPosition(state, mb.ActivationModelWeightedQuadraticBarrier(bounds, weights), sup, nu)
+
+
+def _hmom_cost(mb, state, kind, nu=None):
+    """The synthetic CostModelCentroidalMomentum: a non-zero reference momentum and the
+    activation ``kind`` names (_impulse_cost_activation; the barriers' bounds lie inside the
+    range the random states' momenta cover)."""
+    act = _impulse_cost_activation(mb, kind, 6, -0.3, 0.4)
+    href = (0.3, -0.2, 0.5, 0.02, 0.01, -0.03)
+    args = ([act] if act is not None else []) + [href] + ([nu] if nu is not None else [])
+    return mb.CostModelCentroidalMomentum(state, *args)
 
 
 def _frot_ref(mb):
@@ -395,7 +410,7 @@ ARM_BENT = (0.3, 0.4, -0.2, -1.3, 0.1, 0.6, 0.0)
 
 
 def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, armature=None, w_x=1e-4, w_u=1e-4,
-              frot=False):
+              frot=False, hmom=None):
     """The reference's arm-manipulation problem (benchmark/factory/arm.hpp:31-96,
     benchmark/arm-manipulation-optctrl.cpp:20-40) on real multibody knots:
     Euler(dt) ∘ DifferentialActionModelFreeFwdDynamics with costs
@@ -406,7 +421,8 @@ def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, ar
     ``weighted`` adds a weighted xReg activation and a FrameTranslation cost
     (parity coverage of the remaining cost / activation kinds). w_x / w_u: the
     xReg / uReg weights (the factory's 1e-4 by default). ``frot`` adds a
-    CostModelFrameRotation on the gripper."""
+    CostModelFrameRotation on the gripper, ``hmom`` a CostModelCentroidalMomentum with the
+    activation it names ("quad", "wquad", "barrier", "wbarrier")."""
     from . import multibody as mb
     _, _, _, T0, B0, _ = CONFIGS["C3_talos_arm"]
     T = T0 if T is None else T
@@ -429,6 +445,8 @@ def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, ar
     costs.addCost("uReg", mb.CostModelControl(state), w_u)
     if frot:
         costs.addCost("gripperRot", mb.CostModelFrameRotation(state, mb.FrameRotation(fid, _frot_ref(mb))), 0.4)
+    if hmom is not None:
+        costs.addCost("hMom", _hmom_cost(mb, state, hmom), 0.3)
     dam = mb.DifferentialActionModelFreeFwdDynamics(state, act, costs)
     if armature is not None:
         dam.armature = armature
@@ -455,7 +473,7 @@ def random_floating_state(model, rng, B, spread=0.3, v_spread=0.5):
 def build_floating(T=4, B=2, seed=0, robot=None, dt=1e-2, contacts=(), gains=(2.0, 1.5), damping=0.0,
                    weighted=False, com=False, force_costs=False, enable_force=None, armature=None, spread=0.3,
                    friction=False, fvel=False, barrier=False, cop=None, cop_weights=None, cop_inactive=False,
-                   frot=False):
+                   frot=False, hmom=None):
     """Floating-base knots (the reference's legged-robot models, on a tree below a
     free-flyer root): Euler(dt) ∘ DifferentialAction{Free,Contact}FwdDynamics with
     ActuationModelFloatingBase (nu = nv - 6). ``contacts``: ("6d" | "3d", frame
@@ -471,7 +489,8 @@ def build_floating(T=4, B=2, seed=0, robot=None, dt=1e-2, contacts=(), gains=(2.
     CostModelContactCoPPosition on every 6D contact (QuadraticBarrier, or
     WeightedQuadraticBarrier with the four ``cop_weights``; with ``cop_inactive`` also
     on a switched-off 6D contact of the mid_site frame); ``frot``: a
-    CostModelFrameRotation on the mid_site frame."""
+    CostModelFrameRotation on the mid_site frame; ``hmom``: a CostModelCentroidalMomentum
+    with the activation it names ("quad", "wquad", "barrier", "wbarrier")."""
     from . import multibody as mb
     rng = np.random.default_rng(seed)
     model = mb.sample_tree(5, seed=3, freeflyer=True) if robot is None else robot
@@ -508,6 +527,8 @@ def build_floating(T=4, B=2, seed=0, robot=None, dt=1e-2, contacts=(), gains=(2.
     if frot:
         costs.addCost("midRot", mb.CostModelFrameRotation(state, mb.FrameRotation(
             model.getFrameId("mid_site"), _frot_ref(mb)), nu), 0.4)
+    if hmom is not None:
+        costs.addCost("hMom", _hmom_cost(mb, state, hmom, nu), 0.3)
     if contacts:
         cm = mb.ContactModelMultiple(state, nu)
         for i, (kind, fname) in enumerate(contacts):

@@ -48,7 +48,8 @@ enum { kJointRec = 27, kCostHdr = 4, kMaxContactRows = 24, kMaxDofs = 64 };
 enum { JOINT_REVOLUTE = 0, JOINT_FREEFLYER = 1 };
 enum { COST_STATE = 1, COST_CONTROL = 2, COST_FRAME_PLACEMENT = 3, COST_FRAME_TRANSLATION = 4, CONTACT_3D = 5,
        CONTACT_6D = 6, COST_CONTACT_FORCE = 7, COST_COM_POSITION = 8, COST_FRICTION_CONE = 9,
-       COST_FRAME_VELOCITY = 10, COST_COP_POSITION = 11, COST_FRAME_ROTATION = 12, COST_IMPULSE_COM = 13 };
+       COST_FRAME_VELOCITY = 10, COST_COP_POSITION = 11, COST_FRAME_ROTATION = 12, COST_IMPULSE_COM = 13,
+       COST_CENTROIDAL_MOMENTUM = 14 };
 enum { ACT_QUAD = 0, ACT_WEIGHTED_QUAD = 1, ACT_QUAD_BARRIER = 2, ACT_WEIGHTED_QUAD_BARRIER = 3 };
 static const double kInactiveForceRow = -2.;  // the contact / impulse exists but is inactive
 
@@ -798,6 +799,36 @@ class CostModelCoMPosition : public CostModelAbstract {
   Vec3 cref_;
 };
 
+// r = hg(q, v) - href (centroidal-momentum.hxx): [linear; angular about the CoM], world axes;
+// Euler knots only. Parity unpinned against the reference binary.
+class CostModelCentroidalMomentum : public CostModelAbstract {
+ public:
+  CostModelCentroidalMomentum(std::shared_ptr<StateMultibody> s, std::shared_ptr<ActivationModelAbstract> a,
+                              const VectorXd& href, int nu)
+      : CostModelAbstract(s, a, 6, nu), href_(href) {
+    if (href_.size() != 6) throw Exception("Invalid argument: href has wrong dimension (it should be 6)");
+  }
+  CostModelCentroidalMomentum(std::shared_ptr<StateMultibody> s, std::shared_ptr<ActivationModelAbstract> a,
+                              const VectorXd& href)
+      : CostModelCentroidalMomentum(s, a, href, s->get_nv()) {}
+  CostModelCentroidalMomentum(std::shared_ptr<StateMultibody> s, const VectorXd& href, int nu)
+      : CostModelCentroidalMomentum(s, nullptr, href, nu) {}
+  CostModelCentroidalMomentum(std::shared_ptr<StateMultibody> s, const VectorXd& href)
+      : CostModelCentroidalMomentum(s, nullptr, href, s->get_nv()) {}
+  int type() const { return COST_CENTROIDAL_MOMENTUM; }
+  const VectorXd& get_href() const { return href_; }
+  void set_href(const VectorXd& href) {
+    if (href.size() != 6) throw Exception("Invalid argument: href has wrong dimension (it should be 6)");
+    href_ = href;
+  }
+
+ protected:
+  void payload(VectorXd& out) const {
+    for (int i = 0; i < 6; ++i) out.push_back(href_[i]);
+  }
+  VectorXd href_;
+};
+
 // r = lambda_contact - fref (contact-force.hxx:33-74); the contact's row offset is
 // resolved by the DAM at packing
 class CostModelContactForce : public CostModelAbstract {
@@ -1264,9 +1295,12 @@ class ActionModelImpulseFwdDynamics : public ActionModelBase {
   }
   void pack(VectorXd& out) const {
     // the contact classes read a contact's data, which an impulse knot has not (their Impulse*
-    // twins read the impulses'); frame velocities are not covered here
+    // twins read the impulses'); frame velocities and the centroidal momentum are not covered
+    // here (an impulse knot runs no kinematics at v)
     for (const auto& kv : costs_->get_costs()) {
       const int ty = kv.second.cost->type();
+      if (kv.second.active && ty == COST_CENTROIDAL_MOMENTUM)
+        throw Exception("crocoddyl_amd: centroidal-momentum costs on impulse knots are not covered");
       const bool force = ty == COST_CONTACT_FORCE || ty == COST_FRICTION_CONE || ty == COST_COP_POSITION;
       if (kv.second.active && (ty == COST_FRAME_VELOCITY || (force && !kv.second.cost->impulse_cost())))
         throw Exception("crocoddyl_amd: frame-velocity / force costs on impulse knots are not covered");

@@ -114,6 +114,11 @@ int fddp_abi_version(void);
  *       r = log3(Rref^T oRf), nr = 3
  *    13 CostModelImpulseCoM (impulse knots only): empty payload, the activation
  *       parameters follow the header; r = Jcom(q) (v+ - v), nr = 3
+ *    14 CostModelCentroidalMomentum (centroidal-momentum.hxx, Euler knots:
+ *       FDDP_KNOT_EULER_FREEFWD / _CONTACTFWD, running and dt = 0 alike): href(6);
+ *       r = hg(q, v) - href, hg of pinocchio::computeCentroidalMomentum ([linear;
+ *       angular about the CoM], world axes), nr = 6; Rx = [dhg/dq, Ag], Ru = 0.
+ *       Refused on FDDP_KNOT_IMPULSEFWD, which runs no kinematics at v (as 10)
  *     On an impulse knot (FDDP_KNOT_IMPULSEFWD) the records 7, 9 and 11 are
  *     CostModelContactImpulse, CostModelImpulseFrictionCone and
  *     CostModelImpulseCoPPosition: the same payloads, row0 indexing the stacked
