@@ -24,6 +24,8 @@
 // ... nor one with a CostModelCentroidalMomentum record (at its register cap the record's
 // evaluation costs it 23 more VGPR spills on every horizon)
 #define MB_CALC_MOMENTUM 0
+// ... nor one with an actuation record (tau = S u): its calc keeps tau = [0_nun; u] only
+#define MB_ACTUATION 0
 #endif
 #include "fast_path.hpp"
 #include "fddp_kernels.hpp"

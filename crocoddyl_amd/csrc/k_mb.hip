@@ -9,6 +9,10 @@
 // kernel and 0.5 % slower on the 256-thread all-LDS kernel, which keep the vector arguments
 #if FDDP_TU_MB == 4
 #define MB_MFMA_SCALAR_SHAPE 1
+// the spilled-plan kernel is built without the actuation record's phases (mb_base.hpp
+// MB_ACTUATION): its code stays what the headline runs, and the launch plan gives a horizon with
+// such a record the all-LDS plan, whose objects carry them (launch_plan.hpp plan_lds)
+#define MB_ACTUATION 0
 #endif
 // (the rollout objects' MB_BLK_UNIFORM and MB_LANE_OPAQUE, k_fwd.hip, stay off in these
 // objects: on the MB_S2 kernel they cost C5 calcDiff 24.0 -> 24.6 and 24.8 ms; that object

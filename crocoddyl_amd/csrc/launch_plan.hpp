@@ -60,6 +60,7 @@ struct LdsPlan {
   bool all_mb = false;          // every knot is a multibody knot
   bool has_icom = false;        // a knot carries a CostModelImpulseCoM record (no FWD_MB rollout)
   bool has_hmom = false;        // a knot carries a CostModelCentroidalMomentum record (no FWD_MB rollout)
+  bool has_act = false;         // a knot carries an actuation record, tau = S u (no FWD_MB rollout, no spilled plan)
   int mb_nj = 0;                // largest multibody tree (dofs)
   int64_t mbw = 0, mbw_fwd = 0, mbd = 0;  // Dev::mbw, mbw_fwd, mbd
   int mbspill = 0, dxv_mbw = 0;           // Dev::mbspill, dxv_mbw
@@ -116,7 +117,7 @@ struct Refusal {
 // dofs, jac costs and contact rows (LDS sizing).
 inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, int nu, Refusal& why, int* nj_out,
                               int* njac_out, int* nc_out, bool* vcols_out = nullptr, int* nu_out = nullptr,
-                              int* nrows_out = nullptr) {
+                              int* nrows_out = nullptr, bool* act_out = nullptr) {
   using namespace fddp::mb;
   if (avail < FDDP_PARAM_HEADER) return why = "block out of range", -1;
   const double dt = P[0];
@@ -227,15 +228,22 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
     o += rs;
   }
   int nc = 0;
+  bool act = false;  // flag bit 4: an actuation record after the contacts
   std::vector<std::pair<int, int>> crow;  // (row0, rows) of every contact record
-  if (contact || impulse) {  // [nun | r_coeff, damping, ncontact, 0 | 2 (contact), 1 | 3 (impulse)] + records
+  if (contact || impulse) {  // [nun | r_coeff, damping, ncontact, 0 | 2 | 4 | 6 (contact), 1 | 3 (impulse)] + records
     if (o + 4 > size) return why = "contact section out of range", -1;
     const int nun = (int)P[o], ncon = (int)P[o + 2];
     const double damping = P[o + 1];
-    if (impulse ? (P[o + 3] != 1. && P[o + 3] != 3.) : (P[o + 3] != 0. && P[o + 3] != 2.))
+    if (impulse && (P[o + 3] == 5. || P[o + 3] == 7.)) return why = "impulse knots take no actuation record (nu = 0)", -1;
+    if (impulse ? (P[o + 3] != 1. && P[o + 3] != 3.)
+                : (P[o + 3] != 0. && P[o + 3] != 2. && P[o + 3] != 4. && P[o + 3] != 6.))
       return why = "contact / impulse section flag does not match the kind", -1;
+    act = contact && ((int)P[o + 3] & 4) != 0;
     if (impulse) {
       if (!(P[o] >= 0.) || !std::isfinite(P[o])) return why = "The restitution coefficient has to be positive", -1;
+    } else if (act) {
+      if (P[o] != 0.) return why = "an actuation record needs nun = 0 in the section header", -1;
+      if (nu < 1 || nu > nj) return why = "actuation record: nu out of [1, nv]", -1;
     } else {
       if ((double)nun != P[o] || nun < 0 || nun >= nj) return why = "unactuated dofs out of [0, nv)", -1;
       if (ff && nun != 6) return why = "ActuationModelFloatingBase on a free-flyer leaves 6 dofs unactuated", -1;
@@ -263,6 +271,17 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
       o += rs;
     }
     if (nc > kMaxNc) return why = "more than 24 contact rows in one knot", -1;
+    if (act) {  // [20, 0, 0, 4 + nv nu] + S (nv x nu, column-major): tau = S u
+      if (o + kCHdr > size) return why = "block ends before its actuation record", -1;
+      const double* A = P + o;
+      if (A[0] != (double)C_ACTUATION) return why = "actuation record of the wrong type", -1;
+      const int64_t want = kCHdr + (int64_t)nj * nu;
+      if (A[3] != (double)want) return why = "actuation record of the wrong size", -1;
+      if (o + want > size) return why = "block ends before its actuation record", -1;
+      for (int64_t e = 0; e < (int64_t)nj * nu; ++e)
+        if (!std::isfinite(A[kCHdr + e])) return why = "non-finite entry in the actuation matrix", -1;
+      o += want;
+    }
   }
   if (force_rows > nc)
     return why = impulse ? "impulse cost reads rows beyond the impulses" : "contact-force cost reads rows beyond the contacts", -1;
@@ -283,7 +302,7 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
   if (njac > kMaxJacCosts) return why = "more than 8 frame / CoM / frame-velocity / free-flyer state costs in one knot", -1;
   const int nrows = count_cost_rows(parse(P), nu);
   if (nrows > kMaxCostRows) return why = "more than 64 cost residual rows with dense Jacobians in one knot", -1;
-  if ((pad2(diff_layout(nj, njac, nc, vcols, nu, nrows).total) + pad2(size)) * 8 > 160 * 1024)
+  if ((pad2(diff_layout(nj, njac, nc, vcols, nu, nrows, 0, act).total) + pad2(size)) * 8 > 160 * 1024)
     return why = "too many dofs for the calcDiff LDS plan", -1;
   if (nj_out) *nj_out = std::max(*nj_out, nj);
   if (njac_out) *njac_out = std::max(*njac_out, njac);
@@ -291,6 +310,7 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
   if (vcols_out) *vcols_out = *vcols_out || vcols;
   if (nu_out) *nu_out = std::max(*nu_out, nu);
   if (nrows_out) *nrows_out = std::max(*nrows_out, nrows);
+  if (act_out) *act_out = *act_out || act;
   return size;
 }
 
@@ -306,7 +326,7 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
   int64_t pmax = 0;
   int64_t mb_pmax = 0;  // largest multibody parameter block (staged in LDS by mb_knot_kernel)
   int mb_nj = 0, mb_njac = 0, mb_nc = 0;
-  bool mb_vcols = false;
+  bool mb_vcols = false, mb_act = false;
   int mb_nu = 0, mb_nrows = 0;
   // each multibody block's own shape: the device lays out a knot's calcDiff LDS from its
   // own block, so the plan to allocate is the largest knot's, not the plan of the largest
@@ -314,7 +334,7 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
   // one workgroup per CU, against the largest knot's 79.6 KB)
   struct MbShape {
     int nj, njac, nc, nu, nrows;
-    bool vcols;
+    bool vcols, act;
   };
   std::vector<MbShape> shapes;
   const char* refused = nullptr;  // the first block refusal
@@ -328,12 +348,13 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
       for (int b = 0; b < nb; ++b) {
         const int64_t off = knots[t].param_offset + (int64_t)b * knots[t].param_stride;
         Refusal why;
-        MbShape k{0, 0, 0, 0, 0, false};
+        MbShape k{0, 0, 0, 0, 0, false, false};
         const int64_t s1 = mb_block_check(params + off, n_params - off, knots[t].kind, d.nx, knots[t].nu, why, &k.nj,
-                                          &k.njac, &k.nc, &k.vcols, &k.nu, &k.nrows);
+                                          &k.njac, &k.nc, &k.vcols, &k.nu, &k.nrows, &k.act);
         if (s1 < 0 && !refused) refused = why.text;
         if (s1 >= 0 && fddp::mb::has_impulse_com(fddp::mb::parse(params + off))) p.has_icom = true;
         if (s1 >= 0 && fddp::mb::has_momentum(fddp::mb::parse(params + off))) p.has_hmom = true;
+        if (s1 >= 0 && k.act) p.has_act = true;
         // (a refused block is planned with its size field, as mb_pmax is: the budget below
         // then refuses only what is over it)
         const int64_t own = (int64_t)params[off + 3];
@@ -343,12 +364,13 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
         mb_njac = std::max(mb_njac, k.njac);
         mb_nc = std::max(mb_nc, k.nc);
         mb_vcols = mb_vcols || k.vcols;
+        mb_act = mb_act || k.act;
         mb_nu = std::max(mb_nu, k.nu);
         mb_nrows = std::max(mb_nrows, k.nrows);
         bool seen = false;
         for (const MbShape& q : shapes)
           seen = seen || (q.nj == k.nj && q.njac == k.njac && q.nc == k.nc && q.nu == k.nu && q.nrows == k.nrows &&
-                          q.vcols == k.vcols);
+                          q.vcols == k.vcols && q.act == k.act);
         if (!seen) shapes.push_back(k);
       }
     } else {
@@ -371,14 +393,17 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
   auto plan_doubles = [&](int spill) {  // the largest knot's plan under spill flags `spill`
     int64_t mx = 0;
     for (const MbShape& q : shapes)
-      mx = std::max<int64_t>(mx, pad2(fddp::mb::diff_layout(q.nj, q.njac, q.nc, q.vcols, q.nu, q.nrows, spill).total));
+      mx = std::max<int64_t>(
+          mx, pad2(fddp::mb::diff_layout(q.nj, q.njac, q.nc, q.vcols, q.nu, q.nrows, spill, q.act).total));
     return mx;
   };
   p.mb_all_lds = p.has_mb ? (plan_doubles(0) + pad2(mb_pmax)) * 8 : 0;
   // (the spill flags themselves from the largest value of every parameter: the spilled
   // arrays must fit their output blocks on every knot)
-  p.mbspill = p.has_mb && ov.mb_spill != 0 && p.mb_all_lds > kLdsTwoPerCu
-                  ? fddp::mb::diff_spill(mb_nj, mb_njac, mb_nc, mb_vcols, mb_nu, mb_nrows, mb_pmax, d.nu_max)
+  // (a horizon with an actuation record never spills: the spilled plan's kernel is built without
+  // the record's phases, MB_ACTUATION in k_mb.hip; every accepted block fits the all-LDS plan)
+  p.mbspill = p.has_mb && !mb_act && ov.mb_spill != 0 && p.mb_all_lds > kLdsTwoPerCu
+                  ? fddp::mb::diff_spill(mb_nj, mb_njac, mb_nc, mb_vcols, mb_nu, mb_nrows, mb_pmax, d.nu_max, mb_act)
                   : 0;
   p.mbd = p.has_mb ? plan_doubles(p.mbspill) : 0;
   p.mb_diff_smem = p.has_mb ? sizeof(double) * (p.mbd + pad2(mb_pmax)) : 0;
@@ -419,6 +444,8 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
     p.error = "FDDP_FWD_MBW=3 on a horizon with an impulse CoM cost: that rollout build does not evaluate it";
   if (!p.error && p.has_hmom && ov.fwd_mbw == 3)
     p.error = "FDDP_FWD_MBW=3 on a horizon with a centroidal-momentum cost: that rollout build does not evaluate it";
+  if (!p.error && p.has_act && ov.fwd_mbw == 3)
+    p.error = "FDDP_FWD_MBW=3 on a horizon with an actuation record: that rollout build does not evaluate it";
   return p;
 }
 
@@ -458,10 +485,10 @@ inline VariantPlan plan_variants(const LdsPlan& l, const fddp_dims& d, const Ove
     v.fwd = ktab::FWD_GENERIC;
   } else {
     const bool three = resident_per_cu(f.fwd_api[ktab::FWD_MB], l.fwd_smem, f.fwd_static[ktab::FWD_MB]) >= 3;
-    // (a horizon with an impulse CoM or a centroidal-momentum cost never: that build's calc has
-    // no code for them, MB_CALC_IMPULSE_COM / MB_CALC_MOMENTUM; plan_lds refuses the override
-    // that would force it)
-    const bool take3 = !l.has_icom && !l.has_hmom && (ov.fwd_mbw ? ov.fwd_mbw == 3 : (three && d.B > 2 * cus));
+    // (a horizon with an impulse CoM or a centroidal-momentum cost or an actuation record never:
+    // that build's calc has no code for them, MB_CALC_IMPULSE_COM / MB_CALC_MOMENTUM /
+    // MB_ACTUATION; plan_lds refuses the override that would force it)
+    const bool take3 = !l.has_icom && !l.has_hmom && !l.has_act && (ov.fwd_mbw ? ov.fwd_mbw == 3 : (three && d.B > 2 * cus));
     v.fwd = take3 ? ktab::FWD_MB : ktab::FWD_MB2;
   }
   if (!l.fast) v.ls_slots = (double)cus * resident_per_cu(f.fwd_api[v.fwd], l.fwd_smem, f.fwd_static[v.fwd]);

@@ -109,6 +109,13 @@ MB_HD __forceinline__ T* mb_lds(T* p) {
 #ifndef MB_CALC_MOMENTUM
 #define MB_CALC_MOMENTUM 1
 #endif
+// MB_ACTUATION (per kernel object): the knot evaluates the actuation record (tau = S u, section
+// flag bit 4). As the two switches above: the three-waves-per-EU rollout object and the
+// spilled-plan calcDiff object (the headline's two kernels) are built without it, and the launch
+// plan never gives them a horizon with such a record (LdsPlan::has_act, plan_lds, plan_variants).
+#ifndef MB_ACTUATION
+#define MB_ACTUATION 1
+#endif
 
 namespace fddp {
 namespace mb {
@@ -144,6 +151,7 @@ enum {
   C_CENTROIDAL_MOMENTUM = 14  // r = hg(q, v) - href, hg = [linear; angular about the CoM], world axes: payload
                               // [href(6)] (centroidal-momentum.hxx); Euler knots only
 };
+constexpr int C_ACTUATION = 20;  // the actuation record after the contact records: S (nv x nu, column-major)
 // Activation of a cost record: header slot 2 (core/activations/*.hpp)
 enum { A_QUAD = 0, A_WEIGHTED_QUAD = 1, A_QUAD_BARRIER = 2, A_WEIGHTED_QUAD_BARRIER = 3 };
 constexpr int kInactiveForceRow = -2;  // force cost on an inactive contact / impulse: lambda = 0, no Jacobians
@@ -161,6 +169,8 @@ struct Blk {
   const double* C;    // cost records
   // contact section (DifferentialActionModelContactFwdDynamics); ncon == 0 without
   int nun;            // leading unactuated dofs: tau = [0_nun; u], nu = nj - nun
+                      // (with an actuation record: nj - nu, so that nu = nj - nun holds everywhere)
+  const double* S;    // the actuation record's matrix dtau/du (nj x nu, column-major): tau = S u; null without
   int ncon, nc;       // active contact records, stacked rows
   double damping;     // JMinvJt_damping
   const double* K;    // contact records
@@ -169,6 +179,28 @@ struct Blk {
   double r_coeff;     // restitution coefficient
   bool enable_force;  // section flag bit 2 (contact: 2, impulse: 3): the multiplier Jacobians of the force costs
 };
+// Row i of S u (S nj x nu column-major and u in LDS on the device). Out of line there: a knot
+// without the record pays a uniform branch around a call, and the kernels' register allocation
+// around it stays what it was (inlined it sent the rollout's split gains loop's arrays to scratch,
+// as the momentum record did: MB_MOMENTUM_OUTLINE).
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __attribute__((noinline)) double act_row_dot(const double* S_, const double* u_, int nj, int nu, int i) {
+  const double* S = ::fddp::lds_ptr(S_);
+  const double* u = ::fddp::lds_ptr(u_);
+#else
+inline double act_row_dot(const double* S, const double* u, int nj, int nu, int i) {
+#endif
+  double s = 0.;
+  for (int c = 0; c < nu; ++c) s += S[(int64_t)c * nj + i] * u[c];
+  return s;
+}
+// tau_i of the knot's actuation at u (nu entries): S u with an actuation record, else [0_nun; u]
+MB_HD __forceinline__ double act_tau(const Blk& b, const double* u, int i) {
+#if MB_ACTUATION
+  if (b.S) return act_row_dot(b.S, u, b.nj, b.nj - b.nun, i);
+#endif
+  return i < b.nun ? 0. : u[i - b.nun];
+}
 
 MB_HD inline Blk parse(const double* P) {
   Blk b;
@@ -191,6 +223,7 @@ MB_HD inline Blk parse(const double* P) {
   b.impulse = false;
   b.enable_force = false;
   b.r_coeff = 0.;
+  b.S = nullptr;
   if (e - P < (int64_t)P[3]) {  // [nun | r_coeff, damping, ncontact, 0 | 1 | 2 | 3] + records
     b.impulse = ((int)e[3] & 1) != 0;
     b.enable_force = ((int)e[3] & 2) != 0;
@@ -204,6 +237,12 @@ MB_HD inline Blk parse(const double* P) {
       b.nc += (int)r[0] == C_CONTACT_3D ? 3 : 6;
       r += (int)r[3];
     }
+#if MB_ACTUATION
+    if (((int)e[3] & 4) != 0) {  // [20, 0, 0, 4 + nv nu] + S: tau = S u
+      b.nun = b.nj - ((int)r[3] - 4) / b.nj;
+      b.S = r + 4;
+    }
+#endif
   }
   return b;
 }
@@ -248,6 +287,7 @@ MB_HD __forceinline__ Blk parse_uniform(const double* P) {
   b.J = mb_uniform(b.J);
   b.C = mb_uniform(b.C);
   b.nun = mb_uniform(b.nun);
+  b.S = b.S ? mb_uniform(b.S) : nullptr;
   b.ncon = mb_uniform(b.ncon);
   b.nc = mb_uniform(b.nc);
   b.damping = mb_uniform(b.damping);

@@ -777,7 +777,7 @@ MB_HD __forceinline__ double knot_calc_x(const X& ex, const double* P, int nx, c
   if (!imp) world_rnea(ex, b, W, x + nq, nullptr, tau);
   ex.run([&](int lane) {
     if (lane < nj) {
-      const double ti = lane < b.nun ? 0. : ub[lane - b.nun];  // ActuationModelFloatingBase: tau = [0; u]
+      const double ti = act_tau(b, ub, lane);  // tau = [0_nun; u], or S u with an actuation record
       if (!imp) A[(int64_t)lda * (nj + nc) + lane] = ti - tau[lane];
       if (nc) contact_jac_lane(b, W, lane, Jc, A, lda);
     }
@@ -1000,7 +1000,7 @@ MB_HD __forceinline__ double knot_calc_dense_x(const X& ex, const double* P, int
   });
   ex.run([&](int lane) {
     if (lane < nj) {
-      const double ti = lane < b.nun ? 0. : ub[lane - b.nun];  // ActuationModelFloatingBase: tau = [0; u]
+      const double ti = act_tau(b, ub, lane);  // tau = [0_nun; u], or S u with an actuation record
       if (!imp) A[(int64_t)lda * (nj + nc) + lane] = ti - tau[lane];
       if (nc) contact_jac_lane(b, W, lane, Jc, A, lda);
     }
@@ -1139,6 +1139,9 @@ struct DiffLayout {
   // the cost table's diagonal terms and residual rows (after the table, or apart from it),
   // and the LDS copy of dtau the da product reads (the spilled plan: over the world values)
   int64_t Rr, dts;
+  // with an actuation record: Kinv_atau S (nj x nu at ld lda_of(nj)), da phase .. Fu; -1 without
+  // (all-LDS plan: over the first half of A; spilled plan: an area of its own)
+  int64_t KS, ksz;
   int spill;       // kSpill* flags the plan was made with
   int64_t ht;      // host emulation: its factorisation scratch (70 nj)
   int64_t htotal;  // host emulation: total plus its own areas (da, the factorisation scratch)
@@ -1169,10 +1172,12 @@ MB_HD __forceinline__ int64_t cost_area_doubles(int nj, int nu, int nrows) {
   return cost_table_doubles() + kMaxCostCols + (int64_t)nrows * cost_rows_ld(nj, nu);
 }
 __host__ __device__ inline DiffLayout diff_layout(int nj, int njac, int nc = 0, bool vel_cols = false, int nu = 0,
-                                                  int nrows = 0, int spill = 0) {
+                                                  int nrows = 0, int spill = 0, bool act = false) {
   const int L = 2 * nj;
   DiffLayout l;
   l.spill = spill;
+  l.KS = -1;
+  l.ksz = act ? (int64_t)lda_of(nj) * nu : 0;
   const int64_t jsz = (int64_t)6 * (vel_cols ? L : nj) * (njac > 0 ? njac : 1);  // jac-cost Jacobians [cost][6][jw]
   const int64_t ca = cost_area_doubles(nj, nu, nrows);
   const int64_t wvs = pad2(WVals::doubles(nj));
@@ -1217,6 +1222,7 @@ __host__ __device__ inline DiffLayout diff_layout(int nj, int njac, int nc = 0, 
     }
     l.Rr = l.R + cost_table_doubles();
     l.dts = l.dtau;
+    if (act) l.KS = l.A;  // over M and its factors, dead since M^-1 (nu <= nj columns at the same ld)
     l.ht = pad2(l.total);  // host: the factorisation scratch
     l.htotal = l.ht + pad2((int64_t)70 * nj);
     return l;
@@ -1287,6 +1293,13 @@ __host__ __device__ inline DiffLayout diff_layout(int nj, int njac, int nc = 0, 
     l.total = l.R + ca;
     l.Rr = l.R + cost_table_doubles();
   }
+  // (the spilled plan reuses the first half of A to the end: an area of its own. No device object
+  // runs this pair today, the launch plan keeps horizons with a record on the all-LDS plan; the
+  // host emulation does)
+  if (act) {
+    l.KS = pad2(l.total);
+    l.total = l.KS + l.ksz;
+  }
   // host emulation: the da area and the factorisation's scratch of its own
   l.da = pad2(l.total);
   l.ht = l.da + pad2((int64_t)nj * (L + 1));
@@ -1297,8 +1310,9 @@ __host__ __device__ inline DiffLayout diff_layout(int nj, int njac, int nc = 0, 
 // of psz doubles) exceeds half the CU's LDS, the tree is large enough for the body maps
 // and their sums (84 nj doubles) to fit in the Fx block (4 nj^2); the Jacobians go to
 // Lxu (2 nj m), d lambda / dx, du to Fu (2 nj m) when they fit.
-MB_HD inline int diff_spill(int nj, int njac, int nc, bool vcols, int nu, int nrows, int64_t psz, int m) {
-  const DiffLayout a = diff_layout(nj, njac, nc, vcols, nu, nrows, 0);
+MB_HD inline int diff_spill(int nj, int njac, int nc, bool vcols, int nu, int nrows, int64_t psz, int m,
+                            bool act = false) {
+  const DiffLayout a = diff_layout(nj, njac, nc, vcols, nu, nrows, 0, act);
   if ((pad2(a.total) + pad2(psz)) * 8 <= 80 * 1024 || 84 * (int64_t)nj > 4 * (int64_t)nj * nj) return 0;
   const int64_t jsz = (int64_t)6 * (vcols ? 2 * nj : nj) * (njac > 0 ? njac : 1);
   const int64_t fsz = pad2((int64_t)nc * 2 * nj) + (int64_t)nc * nj;
@@ -1366,6 +1380,7 @@ MB_HD inline int diff_layout_regions(const DiffLayout& l, int nj, int njac, int 
   add("cost table", l.R, cost_table_doubles(), DP_DA, DP_END);
   add("cost diagonal / rows", l.Rr, cost_area_doubles(nj, nu, nrows) - cost_table_doubles(), DP_RROWS, DP_END);
   if (sp && l.dts >= 0) add("dtau (LDS copy)", l.dts, (int64_t)nj * L, DP_DA, DP_DA);
+  add("Kinv S (actuation record)", l.KS, l.ksz, DP_DA, DP_END);
   return k;
 }
 // 0 when no two regions of the plan overlap in both LDS and live range (and all lie in
@@ -2306,6 +2321,38 @@ MB_HD inline void impulse_com_rows(int lane, int nt, const double* csrc, const d
   }
 }
 
+// The two products of an actuation record (tau = S u, S nj x nu column-major) in the calcDiff, on
+// every lane of the workgroup: d lambda / du (k, c) = -sum_i H(k, i) S(i, c) into dfu (nc x nj,
+// its columns beyond nu zero; null: no force Jacobians) and Kinv_atau S into KS (nj x nu at ld
+// lda). Out of line on the device, as act_row_dot. dfu may be the knot's Fu block (kSpillF).
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __attribute__((noinline)) void act_products(int lane, int nt, const double* S_, const double* Kinv_, int lda,
+                                                       const double* H_, int nj, int nu, int nc, double* dfu,
+                                                       double* KS_) {
+  const double* S = lds_ptr(S_);
+  const double* Kinv = lds_ptr(Kinv_);
+  const double* H = lds_ptr(H_);
+  double* KS = lds_ptr(KS_);
+#else
+inline void act_products(int lane, int nt, const double* S, const double* Kinv, int lda, const double* H, int nj, int nu,
+                         int nc, double* dfu, double* KS) {
+#endif
+  if (dfu)
+    for (int e = lane; e < nc * nj; e += nt) {
+      const int k = e / nj, c = e % nj;
+      double s = 0.;
+      if (c < nu)
+        for (int i = 0; i < nj; ++i) s -= H[(int64_t)k * nj + i] * S[(int64_t)c * nj + i];
+      dfu[e] = s;
+    }
+  for (int e = lane; e < nj * nu; e += nt) {
+    const int c = e / nj, i = e % nj;
+    double s = 0.;
+    for (int k = 0; k < nj; ++k) s += Kinv[(int64_t)k * lda + i] * S[(int64_t)c * nj + k];
+    KS[(int64_t)c * lda + i] = s;
+  }
+}
+
 // SP: the spilled plan fixed at compile time (0 / 1: the device kernels, one variant per
 // plan) or taken from `spill` (-1: the host emulation)
 template <class X, int SP = -1>
@@ -2326,7 +2373,7 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
   // (calc only, Fx == nullptr: the same plan; it ends before any spilled array is used)
   if (SP == 0) spill = 0;
   if (SP == 1) spill |= kSpillBlocks;
-  const DiffLayout l = diff_layout(nj, njac, nc, vcols, nu, nrows, spill);
+  const DiffLayout l = diff_layout(nj, njac, nc, vcols, nu, nrows, spill, b.S != nullptr);
   const bool spilled = SP >= 0 ? SP == 1 : (spill & kSpillBlocks) != 0;
   // the recursions' per-wave partials (free areas of their phases: DiffLayout)
   const WVals W{w + l.wv, nj, w + l.pk};
@@ -2442,6 +2489,17 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
   bool ok = tree_minv(ex, b, A, lda, tw, Minv);
   Minv = ex.lds(Minv);
   MB_DUMP(4, Minv, nj, nj, lda);
+#if MB_ACTUATION
+  // (an actuation record: tau = S u once per dof, -(tau - nle) over nle, which is dead after
+  // the next phase; the branch is uniform)
+  const double* const Sa = (b.S && !imp) ? ex.lds(b.S) : nullptr;
+  if (Sa)
+    ex.run([&](int lane) {
+      if (lane < nj) nle[lane] = -(act_tau(b, u, lane) - nle[lane]);
+    });
+#else
+  const double* const Sa = nullptr;
+#endif
   // z = (M + A)^-1 (tau - nle) (the acceleration without contacts); Y = Minv Jc^T
   ex.run([&](int lane) {
     if (lane < nj && imp) {
@@ -2451,7 +2509,10 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
         for (int e = 0; e < 6; ++e) W.root_a()[e] = 0.;  // the impulse RNEA has no gravity
     } else if (lane < nj) {
       double s = 0.;
-      for (int k = 0; k < nj; ++k) s += Minv[(int64_t)k * lda + lane] * ((k < b.nun ? 0. : u[k - b.nun]) - nle[k]);
+      if (Sa)
+        for (int k = 0; k < nj; ++k) s += Minv[(int64_t)k * lda + lane] * (0. - nle[k]);
+      else
+        for (int k = 0; k < nj; ++k) s += Minv[(int64_t)k * lda + lane] * ((k < b.nun ? 0. : u[k - b.nun]) - nle[k]);
       av[lane] = ok ? s : NAN;
     }
     for (int e = lane; e < nj * nc; e += ex.nt) {
@@ -2747,11 +2808,15 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
             ex.lds(dfx)[o] = s;
         }
       }
-      for (int e = lane; e < nc * nj; e += ex.nt) {
-        const int k = e / nj, c = e % nj;
-        dfu[e] = c < nu ? -H[(int64_t)k * nj + b.nun + c] : 0.;
-      }
+      if (!Sa)
+        for (int e = lane; e < nc * nj; e += ex.nt) {
+          const int k = e / nj, c = e % nj;
+          dfu[e] = c < nu ? -H[(int64_t)k * nj + b.nun + c] : 0.;
+        }
     }
+    // an actuation record: d lambda / du = -H^T S and da / du = Kinv_atau S (what the Fu assembly
+    // reads), each formed once per knot
+    if (Sa) act_products(lane, ex.nt, Sa, ex.lds(Minv), lda, ex.lds(H), nj, nu, nc, fd ? dfu : nullptr, ex.lds(w + l.KS));
     // the cost-derivative table: groups in cost (name) order, each the rows of one cost
     // with a dense residual Jacobian, or the diagonal of a state / control cost; per row
     // Arr (hess), and Ar as amul * aval (the quadratic kinds' (w, r), so the gradient
@@ -2846,7 +2911,9 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
     // the operands re-asserted as LDS here: without it the inference lost them and they
     // were flat loads, each waiting (vmcnt) for the output stores issued before it
     const double* const daL = ex.lds(da);
-    const double* const MinvL = ex.lds(Minv);
+    // (with an actuation record: Kinv_atau S, its column c where the other path reads column
+    // nun + c of Kinv_atau)
+    const double* const MinvL = ex.lds(Sa ? w + l.KS : Minv);
     const double* const HL = ex.lds(H);
     const double* const JcL = ex.lds(Jc);
     const double* const JeL = ex.lds(Je);
@@ -2855,7 +2922,7 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
     // the kernel they were reloaded in every iteration, and a scratch reload after an
     // output store waits (vmcnt, in order) for that store to reach memory
     const int NJ = mb_launder(nj), NC = mb_launder(nc), LD = mb_launder(Ld), NU = mb_launder(nu);
-    const int LDA = mb_launder(lda), NUN = mb_launder(b.nun), N = mb_launder(n), M = mb_launder(m);
+    const int LDA = mb_launder(lda), NUN = mb_launder(Sa ? 0 : b.nun), N = mb_launder(n), M = mb_launder(m);
     const double DT = mb_launder(dt), DT2 = mb_launder(dt2);
     const int flags = mb_launder((imp ? 1 : 0) | (integ ? 2 : 0) | (ffe ? 4 : 0) | (ok ? 8 : 0));
     const bool IMP = flags & 1, INTEG = flags & 2, FFE = flags & 4, OK = flags & 8;
@@ -2881,8 +2948,8 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
       if (i < NJ) return daL[(int64_t)i * LD + c] * DT2 + (c == NJ + i ? DT : 0.) + (c == i ? 1. : 0.);
       return daL[(int64_t)(i - NJ) * LD + c] * DT + (c == i ? 1. : 0.);
     };
-    // Fu(i, c) = Kinv_tl(i mod nj, nun + c) dt^2 | dt (dtau/du = [0; I]), Jexp6 on
-    // the free-flyer rows
+    // Fu(i, c) = Kinv_tl(i mod nj, nun + c) dt^2 | dt (dtau/du = [0; I]; with an actuation
+    // record (Kinv_tl S)(i mod nj, c)), Jexp6 on the free-flyer rows
     auto fu_at = [=](int i, int c) __attribute__((always_inline)) -> double {
       if (!(INTEG && c < NU && !IMP)) return 0.;
       if (i < NJ && FFE && i < 6) {

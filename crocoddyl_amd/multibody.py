@@ -8,6 +8,8 @@ Reference API mirrored:
   StateMultibody(model)                         multibody/states/multibody.hxx
   ActuationModelFull(state)                     multibody/actuations/full.hpp
   ActuationModelFloatingBase(state)             multibody/actuations/floating-base.hpp
+  ActuationModelMultiCopterBase(state, n, tau_f) multibody/actuations/multicopter-base.hpp
+  ActuationModelLinear(state, S)                tau = S u, S constant (a project extension)
   ActivationModelQuad(nr), ActivationModelWeightedQuad(weights)
                                                 core/activations/{quadratic,weighted-quadratic}.hpp
   CostModelSum(state, nu).addCost(name, cost, weight)   multibody/costs/cost-sum.hxx:18-85
@@ -587,6 +589,80 @@ class ActuationModelFloatingBase:
         model = state.pinocchio
         self.nun = 6 if model.has_freeflyer else 1
         self.nu = state.nv - self.nun
+
+
+ACTUATION_REC = 20  # record type of the actuation matrix after the contact records (include/fddp_hip.h)
+
+
+class ActuationModelLinear:
+    """tau = S u with a constant S = dtau/du (nv x nu, 1 <= nu <= nv). A project extension, not a
+    class of the reference: it plays the part of a user's own ActuationModelAbstract subclass
+    whose dtau_du is constant and whose dtau_dx is zero (the reference example's
+    ActuationModelDoublePendulum). ``S`` may carry a leading batch axis (B, nv, nu): one matrix
+    per problem of the batch (per-element parameter blocks). Assigning ``S`` anew re-uploads."""
+
+    def __init__(self, state, S):
+        self.state = state
+        self._version = 0
+        self.S = S
+
+    @property
+    def S(self):
+        return self._S.copy()
+
+    @S.setter
+    def S(self, S):
+        S = np.array(S, np.float64)
+        nv = self.state.nv
+        if S.ndim not in (2, 3) or S.shape[-2] != nv:
+            raise ValueError(f"Invalid argument: S has wrong dimension (it should be {nv} x nu)")
+        nu = S.shape[-1]
+        if nu < 1 or nu > nv:
+            raise ValueError(f"Invalid argument: the device path holds 1 <= nu <= nv (nu = {nu}, nv = {nv})")
+        if not np.isfinite(S).all():
+            raise ValueError("Invalid argument: S has a non-finite entry")
+        if hasattr(self, "nu") and nu != self.nu:
+            raise ValueError(f"Invalid argument: S has wrong dimension (it should be {nv} x {self.nu})")
+        self._S, self.nu = S, nu
+        self._version += 1
+
+    def matrix(self, b=0):
+        """S of batch element b (the one matrix when there is no batch axis)."""
+        return self._S[b].copy() if self._S.ndim == 3 else self._S.copy()
+
+    def pack(self):
+        """(Bm, 4 + nv nu) rows of the actuation record: [20, 0, 0, size] + S column-major."""
+        S = self._S if self._S.ndim == 3 else self._S[None]
+        flat = S.transpose(0, 2, 1).reshape(S.shape[0], -1)
+        hdr = np.broadcast_to(np.array([ACTUATION_REC, 0.0, 0.0, 4 + flat.shape[1]]), (S.shape[0], 4))
+        return np.concatenate([hdr, flat], axis=1)
+
+
+class ActuationModelMultiCopterBase(ActuationModelLinear):
+    """ActuationModelMultiCopterBase(state, n_rotors, tau_f)
+    (multibody/actuations/multicopter-base.hpp): a free-flyer base driven by n_rotors rotor
+    thrusts through tau_f (6 x n_rotors), the other joints actuated one to one:
+    nu = nv - 6 + n_rotors, S = [[tau_f, 0], [0, I_{nv-6}]]. ``tau_f`` may carry a leading
+    batch axis (B, 6, n_rotors)."""
+
+    def __init__(self, state, n_rotors, tau_f):
+        if not state.pinocchio.has_freeflyer:
+            raise ValueError("Invalid argument: the first joint has to be free-flyer")
+        tau_f = np.array(tau_f, np.float64)
+        n_rotors = int(n_rotors)
+        if tau_f.ndim not in (2, 3) or tau_f.shape[-2:] != (6, n_rotors):
+            raise ValueError(f"Invalid argument: tau_f has wrong dimension (it should be 6 x {n_rotors})")
+        nv = state.nv
+        if n_rotors > 6:
+            raise ValueError(f"Invalid argument: nu = {nv - 6 + n_rotors} exceeds nv = {nv}: the device path "
+                             "holds actuations with nu <= nv only")
+        self.n_rotors = n_rotors
+        self.tau_f = tau_f
+        lead = tau_f.shape[:-2]
+        S = np.zeros(lead + (nv, nv - 6 + n_rotors))
+        S[..., :6, :n_rotors] = tau_f
+        S[..., 6:, n_rotors:] = np.eye(nv - 6)
+        super().__init__(state, S)
 
 
 ACT_QUAD, ACT_WEIGHTED_QUAD, ACT_QUAD_BARRIER, ACT_WEIGHTED_QUAD_BARRIER = 0, 1, 2, 3
@@ -1340,15 +1416,16 @@ class DifferentialActionModelFreeFwdDynamics(_ControlLimits):
     (tau - nle) once an armature is set), cost = costs.calc(x, u)."""
 
     def __init__(self, state, actuation, costs):
-        if not isinstance(actuation, (ActuationModelFull, ActuationModelFloatingBase)):
-            raise NotImplementedError("crocoddyl_amd: the device path covers ActuationModelFull and "
-                                      "ActuationModelFloatingBase only")
+        if not isinstance(actuation, (ActuationModelFull, ActuationModelFloatingBase, ActuationModelLinear)):
+            raise NotImplementedError("crocoddyl_amd: the device path covers ActuationModelFull, "
+                                      "ActuationModelFloatingBase, ActuationModelMultiCopterBase and "
+                                      "ActuationModelLinear only")
         self._init_dam(state, actuation, costs)
 
     @property
     def knot_kind(self):
-        """Device knot kind of Euler(this DAM): free dynamics with a floating-base
-        actuation is the contact knot with an empty ContactModelMultiple."""
+        """Device knot kind of Euler(this DAM): free dynamics with a floating-base or a
+        linear (tau = S u) actuation is the contact knot with an empty ContactModelMultiple."""
         return _abi.KNOT_EULER_FREEFWD if isinstance(self.actuation, ActuationModelFull) else \
             _abi.KNOT_EULER_CONTACTFWD
 
@@ -1379,13 +1456,16 @@ class DifferentialActionModelFreeFwdDynamics(_ControlLimits):
 
     def version(self):
         return (self.state.pinocchio._version, self.costs._version, self._arm_version,
-                tuple(getattr(c.cost, "_version", 0) for c in self.costs.costs.values()))
+                tuple(getattr(c.cost, "_version", 0) for c in self.costs.costs.values())) + \
+            ((("S", self.actuation._version),) if isinstance(self.actuation, ActuationModelLinear) else ())
 
     def quasiStatic(self, x, maxiter=100, tol=1e-9):
         """u holding x = (q, 0) still (free-fwddyn.hxx:137-160): pinv(dtau/du) g(q),
         i.e. g(q) on the actuated dofs. Host-side setup (warm starts), not the device path."""
         x = np.asarray(x, float)
         g = self.state.pinocchio.computeGeneralizedGravity(x[:self.state.nq])
+        if isinstance(self.actuation, ActuationModelLinear):
+            return np.linalg.pinv(self.actuation.matrix()) @ g
         return g[self.state.nv - self.nu:].copy()
 
     def pack_body(self, dt):
@@ -1394,6 +1474,10 @@ class DifferentialActionModelFreeFwdDynamics(_ControlLimits):
         _refuse_impulse_costs(self.costs)
         if isinstance(self.actuation, ActuationModelFloatingBase):
             return _pack_mb(self.state, self._armature, self.costs, dt, [self.actuation.nun, 0.0, 0.0, 0.0])
+        if isinstance(self.actuation, ActuationModelLinear):  # section flag bit 4: the actuation record follows
+            rec = self.actuation.pack()
+            sec = np.concatenate([np.broadcast_to([0.0, 0.0, 0.0, 4.0], (rec.shape[0], 4)), rec], axis=1)
+            return _pack_mb(self.state, self._armature, self.costs, dt, sec)
         return _pack_mb(self.state, self._armature, self.costs, dt)
 
 
@@ -1409,7 +1493,10 @@ def _pack_mb(state, armature, costs, dt, section=None):
     model = state.pinocchio
     robot = model.pack_robot(armature).reshape(1, -1)
     recs = costs.pack()
-    parts = [robot] + recs + ([np.asarray(section, float).reshape(1, -1)] if section is not None else [])
+    if section is not None:  # one row, or one row per problem of the batch
+        section = np.asarray(section, float)
+        section = section.reshape(1, -1) if section.ndim == 1 else section
+    parts = [robot] + recs + ([section] if section is not None else [])
     Bm = max(p.shape[0] for p in parts)
     size = _abi.PARAM_HEADER + sum(p.shape[1] for p in parts)
     hdr = np.array([[dt, model.nv, len(recs), size]])
@@ -1557,8 +1644,11 @@ class DifferentialActionModelContactFwdDynamics(DifferentialActionModelFreeFwdDy
     ContactCoPPosition read; without it their residual Jacobians are zero, as in the reference."""
 
     def __init__(self, state, actuation, contacts, costs, inv_damping=0.0, enable_force=False):
-        if not isinstance(actuation, ActuationModelFloatingBase):
-            raise TypeError("DifferentialActionModelContactFwdDynamics needs an ActuationModelFloatingBase")
+        # (the reference's 1.4.0 signature takes the floating base only; the linear actuations are
+        # accepted here beside it)
+        if not isinstance(actuation, (ActuationModelFloatingBase, ActuationModelLinear)):
+            raise TypeError("DifferentialActionModelContactFwdDynamics needs an ActuationModelFloatingBase, an "
+                            "ActuationModelMultiCopterBase or an ActuationModelLinear")
         if not isinstance(contacts, ContactModelMultiple):
             raise TypeError("DifferentialActionModelContactFwdDynamics needs a ContactModelMultiple")
         if contacts.nu != actuation.nu:
@@ -1586,7 +1676,8 @@ class DifferentialActionModelContactFwdDynamics(DifferentialActionModelFreeFwdDy
         model, nv, nu = self.state.pinocchio, self.state.nv, self.nu
         q = x[:self.state.nq]
         g = model.computeGeneralizedGravity(q)
-        cols = [np.vstack([np.zeros((nv - nu, nu)), np.eye(nu)])]
+        cols = [self.actuation.matrix() if isinstance(self.actuation, ActuationModelLinear)
+                else np.vstack([np.zeros((nv - nu, nu)), np.eye(nu)])]
         for n in self.contacts.active:
             c = self.contacts.contacts[n].contact
             J = model.getFrameJacobian(q, c._ref.id)
@@ -1601,8 +1692,13 @@ class DifferentialActionModelContactFwdDynamics(DifferentialActionModelFreeFwdDy
         recs = self.contacts.pack()
         if self.contacts.nc > MAX_CONTACT_ROWS:
             raise ValueError(f"Invalid argument: the device path holds at most {MAX_CONTACT_ROWS} contact rows")
-        sec = np.concatenate([[self.actuation.nun, self.JMinvJt_damping, len(recs), 2.0 if self.enable_force else 0.0]]
-                             + recs)
+        flag = 2.0 if self.enable_force else 0.0
+        if isinstance(self.actuation, ActuationModelLinear):  # flag bit 4: the actuation record after the contacts
+            rec = self.actuation.pack()
+            head = np.concatenate([[0.0, self.JMinvJt_damping, len(recs), flag + 4.0]] + recs)
+            sec = np.concatenate([np.broadcast_to(head, (rec.shape[0], head.size)), rec], axis=1)
+        else:
+            sec = np.concatenate([[self.actuation.nun, self.JMinvJt_damping, len(recs), flag]] + recs)
         out = _pack_mb(self.state, self._armature, self.costs, dt, sec)
         # costs on a contact's force: the row offset of the contact on fref.id among the
         # active contacts; a contact that exists but is inactive has f = 0 and zero force

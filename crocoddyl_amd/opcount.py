@@ -174,6 +174,11 @@ def knot_flops(model):
     dfdx = 2 * (n + nc) ** 2 * L if nc else 2 * n * n * L
     eul = 2 * n * L + (72 * L if robot.has_freeflyer else 0) + 2 * n * nu
     diff = calc + rnea_d + kkt + cder + dfdx + eul + cd
+    if not imp and isinstance(dam.actuation, mb.ActuationModelLinear):
+        # tau = S u (calc), and the two products of the calcDiff formed once per knot:
+        # da/du = Kinv_atau S, and with enable_force d lambda / du = -H^T S
+        calc += 2 * n * nu
+        diff += 2 * n * nu + 2 * n * n * nu + (2 * nc * n * nu if nc and dam.enable_force else 0)
     return float(calc), float(diff)
 
 

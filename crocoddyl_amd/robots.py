@@ -12,6 +12,8 @@ reference configurations), as ``crocoddyl_amd.multibody.RobotModel`` objects.
   sample_talos():  free-flyer + 32 revolute joints (talos_reduced: legs 2 x 6, torso 2,
                    arms 2 x 7 + grippers 2, head 2): nq = 39, nv = 38 (C5)
   sample_solo12(): free-flyer + 4 legs x 3 (HAA, HFE, KFE): nq = 19, nv = 18 (C4)
+  sample_quadrotor(arm_joints=0): a free-flyer base body, optionally with a short revolute
+                   chain below it (nv = 6 + arm_joints); quadrotor_tau_f(): the rotor map
 """
 import numpy as np
 
@@ -121,3 +123,30 @@ def sample_solo12():
     assert q.size == m.nq == 19 and m.nv == 18
     m.referenceConfigurations["standing"] = q
     return m
+
+
+def sample_quadrotor(arm_joints=0):
+    """A quadrotor in the role of the reference examples' hector / iris models: one base body on
+    a free-flyer root (frame ``base_link``), and below it an optional chain of ``arm_joints``
+    short revolute links (``arm_1_joint`` ..., alternating y / x axes, tip frame ``arm_tip``).
+    Built in code: it is not the reference's URDF, only a body of a quadrotor's mass and
+    inertia for the multicopter actuation (quadrotor_tau_f)."""
+    m = RobotModel(JointModelFreeFlyer())
+    _body(m, 1, 1.477, (0.0, 0.0, -0.01), (0.0115, 0.0115, 0.0218))
+    m.addFrame("root_joint", 1)
+    m.addFrame("base_link", 1, SE3(np.eye(3), (0.0, 0.0, 0.0)))
+    if arm_joints:
+        ids = _chain(m, 1, [(f"_{i + 1}_joint", _Y if i % 2 == 0 else _X, (0.0, 0.0, -0.05 if i == 0 else -0.12),
+                             0.12, (0.0, 0.0, -0.06), (4e-4, 4e-4, 5e-5)) for i in range(arm_joints)], "arm")
+        for j in ids:
+            m.setEffortLimit(j, 2.0)
+        m.addFrame("arm_tip", ids[-1], SE3(np.eye(3), (0.0, 0.0, -0.12)))
+    return m
+
+
+def quadrotor_tau_f(d=0.1525, cf=6.6e-5, cm=1e-6):
+    """tau_f (6 x 4) of the reference's quadrotor example: four rotors at arm length d, thrust
+    coefficient cf and moment coefficient cm; thrusts along the base's z axis."""
+    r = cm / cf
+    return np.array([[0.0, 0.0, 0.0, 0.0], [0.0, 0.0, 0.0, 0.0], [1.0, 1.0, 1.0, 1.0], [0.0, d, 0.0, -d],
+                     [-d, 0.0, d, 0.0], [-r, r, -r, r]])

@@ -410,7 +410,7 @@ ARM_BENT = (0.3, 0.4, -0.2, -1.3, 0.1, 0.6, 0.0)
 
 
 def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, armature=None, w_x=1e-4, w_u=1e-4,
-              frot=False, hmom=None):
+              frot=False, hmom=None, actuation=None):
     """The reference's arm-manipulation problem (benchmark/factory/arm.hpp:31-96,
     benchmark/arm-manipulation-optctrl.cpp:20-40) on real multibody knots:
     Euler(dt) ∘ DifferentialActionModelFreeFwdDynamics with costs
@@ -422,7 +422,8 @@ def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, ar
     (parity coverage of the remaining cost / activation kinds). w_x / w_u: the
     xReg / uReg weights (the factory's 1e-4 by default). ``frot`` adds a
     CostModelFrameRotation on the gripper, ``hmom`` a CostModelCentroidalMomentum with the
-    activation it names ("quad", "wquad", "barrier", "wbarrier")."""
+    activation it names ("quad", "wquad", "barrier", "wbarrier"). ``actuation``: None
+    (ActuationModelFull) or a matrix S (nv x nu, or (B, nv, nu)): ActuationModelLinear, tau = S u."""
     from . import multibody as mb
     _, _, _, T0, B0, _ = CONFIGS["C3_talos_arm"]
     T = T0 if T is None else T
@@ -430,23 +431,24 @@ def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, ar
     rng = np.random.default_rng(seed_of("C3_talos_arm") + 1 if seed is None else seed)
     model = mb.sample_talos_arm() if robot is None else robot
     state = mb.StateMultibody(model)
-    act = mb.ActuationModelFull(state)
+    act = mb.ActuationModelFull(state) if actuation is None else _linear_actuation(mb, state, actuation)
+    nu = act.nu
     fid = model.getFrameId("gripper_left_joint") if model.existFrame("gripper_left_joint") else len(model.frames) - 1
     Mref = mb.FramePlacement(fid, mb.SE3(np.eye(3), (0.0, 0.0, 0.4)))
-    costs = mb.CostModelSum(state)
-    costs.addCost("gripperPose", mb.CostModelFramePlacement(state, Mref), 1.0)
+    costs = mb.CostModelSum(state, nu)
+    costs.addCost("gripperPose", mb.CostModelFramePlacement(state, Mref, nu), 1.0)
     if weighted:
         w = np.linspace(0.5, 2.0, state.ndx)
-        costs.addCost("xReg", mb.CostModelState(state, mb.ActivationModelWeightedQuad(w)), w_x)
+        costs.addCost("xReg", mb.CostModelState(state, mb.ActivationModelWeightedQuad(w), state.zero(), nu), w_x)
         costs.addCost("gripperTrans", mb.CostModelFrameTranslation(
-            state, mb.FrameTranslation(fid, (0.1, 0.2, 0.3))), 0.3)
+            state, mb.FrameTranslation(fid, (0.1, 0.2, 0.3)), nu), 0.3)
     else:
-        costs.addCost("xReg", mb.CostModelState(state), w_x)
-    costs.addCost("uReg", mb.CostModelControl(state), w_u)
+        costs.addCost("xReg", mb.CostModelState(state, state.zero(), nu), w_x)
+    costs.addCost("uReg", mb.CostModelControl(state, nu), w_u)
     if frot:
-        costs.addCost("gripperRot", mb.CostModelFrameRotation(state, mb.FrameRotation(fid, _frot_ref(mb))), 0.4)
+        costs.addCost("gripperRot", mb.CostModelFrameRotation(state, mb.FrameRotation(fid, _frot_ref(mb)), nu), 0.4)
     if hmom is not None:
-        costs.addCost("hMom", _hmom_cost(mb, state, hmom), 0.3)
+        costs.addCost("hMom", _hmom_cost(mb, state, hmom, nu), 0.3)
     dam = mb.DifferentialActionModelFreeFwdDynamics(state, act, costs)
     if armature is not None:
         dam.armature = armature
@@ -454,6 +456,17 @@ def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, ar
     terminal = IntegratedActionModelEuler(dam, 0.0)
     x0s = np.hstack([rng.uniform(-1, 1, (B, state.nq)), rng.uniform(-1, 1, (B, state.nv))])
     return x0s, [running] * T, terminal
+
+
+def _linear_actuation(mb, state, actuation):
+    """The builders' ``actuation=`` option: "multicopter" (four rotors on the free-flyer base, the
+    quadrotor example's map) or a matrix S (nv x nu, optionally with a leading batch axis)."""
+    if isinstance(actuation, str):
+        if actuation != "multicopter":
+            raise ValueError(f"unknown actuation {actuation!r}")
+        from . import robots
+        return mb.ActuationModelMultiCopterBase(state, 4, robots.quadrotor_tau_f())
+    return mb.ActuationModelLinear(state, actuation)
 
 
 def random_floating_state(model, rng, B, spread=0.3, v_spread=0.5):
@@ -473,7 +486,7 @@ def random_floating_state(model, rng, B, spread=0.3, v_spread=0.5):
 def build_floating(T=4, B=2, seed=0, robot=None, dt=1e-2, contacts=(), gains=(2.0, 1.5), damping=0.0,
                    weighted=False, com=False, force_costs=False, enable_force=None, armature=None, spread=0.3,
                    friction=False, fvel=False, barrier=False, cop=None, cop_weights=None, cop_inactive=False,
-                   frot=False, hmom=None):
+                   frot=False, hmom=None, actuation=None):
     """Floating-base knots (the reference's legged-robot models, on a tree below a
     free-flyer root): Euler(dt) ∘ DifferentialAction{Free,Contact}FwdDynamics with
     ActuationModelFloatingBase (nu = nv - 6). ``contacts``: ("6d" | "3d", frame
@@ -490,14 +503,16 @@ def build_floating(T=4, B=2, seed=0, robot=None, dt=1e-2, contacts=(), gains=(2.
     WeightedQuadraticBarrier with the four ``cop_weights``; with ``cop_inactive`` also
     on a switched-off 6D contact of the mid_site frame); ``frot``: a
     CostModelFrameRotation on the mid_site frame; ``hmom``: a CostModelCentroidalMomentum
-    with the activation it names ("quad", "wquad", "barrier", "wbarrier")."""
+    with the activation it names ("quad", "wquad", "barrier", "wbarrier"). ``actuation``: None
+    (ActuationModelFloatingBase), "multicopter" (ActuationModelMultiCopterBase with four rotors)
+    or a matrix S (nv x nu, or (B, nv, nu)): ActuationModelLinear, tau = S u."""
     from . import multibody as mb
     rng = np.random.default_rng(seed)
     model = mb.sample_tree(5, seed=3, freeflyer=True) if robot is None else robot
     if not model.existFrame("mid_site"):
         model.addFrame("mid_site", min(3, model.njoints - 1), mb.SE3(np.eye(3), (0.0, 0.05, -0.1)))
     state = mb.StateMultibody(model)
-    act = mb.ActuationModelFloatingBase(state)
+    act = mb.ActuationModelFloatingBase(state) if actuation is None else _linear_actuation(mb, state, actuation)
     nu = act.nu
     tip = model.getFrameId("tip")
     xref = random_floating_state(model, rng, 1, spread=0.5, v_spread=0.2)[0]

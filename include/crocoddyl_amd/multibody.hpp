@@ -12,6 +12,8 @@
 //     JointModelFreeFlyer, JointModelRevoluteUnaligned / RX / RY / RZ
 //   StateMultibody                            multibody/states/multibody.hxx:14-240
 //   ActuationModelFull / ActuationModelFloatingBase   multibody/actuations/{full,floating-base}.hpp
+//   ActuationModelMultiCopterBase                     multibody/actuations/multicopter-base.hpp
+//   ActuationModelLinear (tau = S u, S constant)      a project extension
 //   ActivationModelQuad / WeightedQuad / QuadraticBarrier / WeightedQuadraticBarrier,
 //     ActivationBounds                        core/activations/*.hpp
 //   FrictionCone                              multibody/friction-cone.hxx:24-96
@@ -432,6 +434,9 @@ struct ActuationModelAbstract {
   virtual ~ActuationModelAbstract() {}
   int nu = 0, nun = 0;  // controls; unactuated root dofs (floating base)
   virtual bool floating_base() const = 0;
+  // dtau/du of a linear actuation (nv x nu, column-major: the block's actuation record), or
+  // null: tau = [0_nun; u]
+  virtual const VectorXd* matrix() const { return nullptr; }
 };
 struct ActuationModelFull : ActuationModelAbstract {  // tau = u
   explicit ActuationModelFull(std::shared_ptr<StateMultibody> state) {
@@ -446,6 +451,50 @@ struct ActuationModelFloatingBase : ActuationModelAbstract {  // floating-base.h
     nu = state->get_nv() - nun;
   }
   bool floating_base() const { return true; }
+};
+
+// tau = S u with a constant S = dtau/du (nv x nu, column-major, 1 <= nu <= nv). A project
+// extension, not a class of the reference: it plays the part of a user's own
+// ActuationModelAbstract subclass whose dtau_du is constant and whose dtau_dx is zero (the
+// reference example's ActuationModelDoublePendulum).
+struct ActuationModelLinear : ActuationModelAbstract {
+  ActuationModelLinear(std::shared_ptr<StateMultibody> state, const VectorXd& S, int nu_) { set(state->get_nv(), S, nu_); }
+  bool floating_base() const { return false; }
+  const VectorXd* matrix() const { return &S_; }
+
+ protected:
+  ActuationModelLinear() {}
+  void set(int nv, const VectorXd& S, int nu_) {
+    if (nu_ < 1 || nu_ > nv)
+      throw Exception("Invalid argument: the device path holds 1 <= nu <= nv (nu = " + std::to_string(nu_) +
+                      ", nv = " + std::to_string(nv) + ")");
+    if ((int)S.size() != nv * nu_)
+      throw Exception("Invalid argument: S has wrong dimension (it should be " + std::to_string(nv) + " x nu)");
+    for (double v : S)
+      if (!std::isfinite(v)) throw Exception("Invalid argument: S has a non-finite entry");
+    nu = nu_;
+    S_ = S;
+  }
+  VectorXd S_;
+};
+// multicopter-base.hpp: a free-flyer base driven by n_rotors rotor thrusts through tau_f
+// (6 x n_rotors, row-major here: one row of the reference's matrix after the other), the other
+// joints actuated one to one: nu = nv - 6 + n_rotors, S = [[tau_f, 0], [0, I_{nv-6}]].
+struct ActuationModelMultiCopterBase : ActuationModelLinear {
+  ActuationModelMultiCopterBase(std::shared_ptr<StateMultibody> state, int n_rotors, const VectorXd& tau_f) {
+    if (!state->get_pinocchio()->has_freeflyer()) throw Exception("Invalid argument: the first joint has to be free-flyer");
+    if (n_rotors < 0 || (int)tau_f.size() != 6 * n_rotors)
+      throw Exception("Invalid argument: tau_f has wrong dimension (it should be 6 x " + std::to_string(n_rotors) + ")");
+    const int nv = state->get_nv(), m = nv - 6 + n_rotors;
+    if (n_rotors > 6)
+      throw Exception("Invalid argument: nu = " + std::to_string(m) + " exceeds nv = " + std::to_string(nv) +
+                      ": the device path holds actuations with nu <= nv only");
+    VectorXd S((size_t)nv * m, 0.);
+    for (int i = 0; i < 6; ++i)
+      for (int c = 0; c < n_rotors; ++c) S[(size_t)c * nv + i] = tau_f[(size_t)i * n_rotors + c];
+    for (int i = 6; i < nv; ++i) S[(size_t)(n_rotors + i - 6) * nv + i] = 1.;
+    set(nv, S, m);
+  }
 };
 
 // ---- activations (core/activations/*.hpp) ----------------------------------
@@ -1125,7 +1174,9 @@ class DifferentialActionModelFreeFwdDynamics : public DifferentialActionModelBas
       throw Exception("Invalid argument: Costs doesn't have the same control dimension (it should be " +
                       std::to_string(a->nu) + ")");
   }
-  int euler_kind() const { return actuation_->floating_base() ? FDDP_KNOT_EULER_CONTACTFWD : FDDP_KNOT_EULER_FREEFWD; }
+  int euler_kind() const {
+    return actuation_->floating_base() || actuation_->matrix() ? FDDP_KNOT_EULER_CONTACTFWD : FDDP_KNOT_EULER_FREEFWD;
+  }
   int nx() const { return state_->get_nx(); }
   int ndx() const { return state_->get_ndx(); }
   int nu() const { return actuation_->nu; }
@@ -1137,7 +1188,11 @@ class DifferentialActionModelFreeFwdDynamics : public DifferentialActionModelBas
   const std::shared_ptr<CostModelSum>& get_costs() const { return costs_; }
   const std::shared_ptr<StateMultibody>& get_state() const { return state_; }
   void pack_euler(double dt, VectorXd& out) const {
-    if (actuation_->floating_base()) {
+    if (actuation_->matrix()) {  // section flag bit 4: no contacts, then the actuation record
+      VectorXd sec{0., 0., 0., 4.};
+      pack_actuation(sec);
+      pack_mb(dt, sec.data(), sec.size(), out);
+    } else if (actuation_->floating_base()) {
       const double sec[4] = {(double)actuation_->nun, 0., 0., 0.};
       pack_mb(dt, sec, 4, out);
     } else {
@@ -1159,6 +1214,12 @@ class DifferentialActionModelFreeFwdDynamics : public DifferentialActionModelBas
     out[o + 3] = (double)(out.size() - o);
     return o;
   }
+  // the actuation record [20, 0, 0, 4 + nv nu] + S (column-major), after the contact records
+  void pack_actuation(VectorXd& sec) const {
+    const VectorXd& S = *actuation_->matrix();
+    sec.insert(sec.end(), {20., 0., 0., (double)(4 + S.size())});
+    sec.insert(sec.end(), S.begin(), S.end());
+  }
   std::shared_ptr<StateMultibody> state_;
   std::shared_ptr<ActuationModelAbstract> actuation_;
   std::shared_ptr<CostModelSum> costs_;
@@ -1177,6 +1238,20 @@ class DifferentialActionModelContactFwdDynamics : public DifferentialActionModel
         damping_(std::fabs(inv_damping)), enable_force_(enable_force) {
     if (contacts->get_nu() != a->nu) throw Exception("Invalid argument: Contacts doesn't have the same control dimension");
   }
+  // (the reference's 1.4.0 signature takes the floating base only; this overload also takes the
+  // linear actuations: ActuationModelMultiCopterBase, ActuationModelLinear)
+  DifferentialActionModelContactFwdDynamics(std::shared_ptr<StateMultibody> s,
+                                            std::shared_ptr<ActuationModelAbstract> a,
+                                            std::shared_ptr<ContactModelMultiple> contacts,
+                                            std::shared_ptr<CostModelSum> costs, double inv_damping = 0.,
+                                            bool enable_force = false)
+      : DifferentialActionModelFreeFwdDynamics(s, a, costs), contacts_(contacts),
+        damping_(std::fabs(inv_damping)), enable_force_(enable_force) {
+    if (!a->floating_base() && !a->matrix())
+      throw Exception("Invalid argument: DifferentialActionModelContactFwdDynamics needs an ActuationModelFloatingBase, "
+                      "an ActuationModelMultiCopterBase or an ActuationModelLinear");
+    if (contacts->get_nu() != a->nu) throw Exception("Invalid argument: Contacts doesn't have the same control dimension");
+  }
   int euler_kind() const { return FDDP_KNOT_EULER_CONTACTFWD; }
   const std::shared_ptr<ContactModelMultiple>& get_contacts() const { return contacts_; }
   void pack_euler(double dt, VectorXd& out) const {
@@ -1186,9 +1261,12 @@ class DifferentialActionModelContactFwdDynamics : public DifferentialActionModel
     int nact = 0;
     for (const auto& kv : contacts_->get_contacts())
       if (kv.second.active) ++nact;
-    sec.insert(sec.end(), {(double)actuation_->nun, damping_, (double)nact, enable_force_ ? 2. : 0.});
+    const bool lin = actuation_->matrix() != nullptr;  // flag bit 4: the actuation record after the contacts
+    sec.insert(sec.end(), {lin ? 0. : (double)actuation_->nun, damping_, (double)nact,
+                           (enable_force_ ? 2. : 0.) + (lin ? 4. : 0.)});
     for (const auto& kv : contacts_->get_contacts())
       if (kv.second.active) kv.second.contact->pack(sec);
+    if (lin) pack_actuation(sec);
     const size_t o = pack_mb(dt, sec.data(), sec.size(), out);
     // force / cone costs: the row offset (and rows) of the contact on their frame among
     // the active contacts; an existing but inactive contact has lambda = 0

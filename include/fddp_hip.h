@@ -140,7 +140,15 @@ int fddp_abi_version(void);
  *     placement in that joint R(9) p(3), then 3D: reference translation(3);
  *     6D: Mref^-1 R(9) p(3)
  * At most 24 stacked contact rows (nc); the Schur complement Jc M^-1 Jc^T +
- * damping I must be positive definite (full-rank Jc or damping > 0). */
+ * damping I must be positive definite (full-rank Jc or damping > 0).
+ * Flag bit 4 (flags 4 and 6, this kind only; an impulse section keeps 1 or 3): a
+ * linear actuation tau = S u with a constant S = dtau/du in place of [0_nun; u]
+ * (ActuationModelMultiCopterBase, actuations/multicopter-base.hpp; any actuation with
+ * a constant dtau_du and dtau_dx = 0). Then nun = 0 in the header, and after the
+ * ncontact contact records comes one actuation record
+ *   [type 20, 0, 0, size = 4 + nv nu], S (nv x nu, column-major), 1 <= nu <= nv,
+ * with which the block ends. ncontact = 0 stays allowed (free dynamics under such an
+ * actuation, as under the floating base). A block without bit 4 is read as before. */
 #define FDDP_KNOT_EULER_CONTACTFWD 5
 /* ActionModelImpulseFwdDynamics (multibody/actions/impulse-fwddyn.hxx:53-127): an
  * action model (no integrator), nu = 0, xnext = (q, v+) with the impulse
