@@ -230,11 +230,15 @@ struct Dev {
   double *pxs, *pus, *pxnext, *pkcost, *pdvp;  // slots 1..npar-1: [slot][B][T+1|T][...]
   double* ptrial;                  // [B][npar][4]: ok, cost_try, dv, -
   int* ls_done;                    // [B] line search decided in an earlier group of this iteration
-  __device__ bool box_knot(int b, int t) const { return box && haslim && haslim[(int64_t)b * T + t]; }
+  // The accessors are always inlined: a kernel that calls one out of line passes the address of
+  // its by-value Dev argument, and the whole struct then lives in scratch memory (688 B per lane,
+  // read back at every use; the inliner left box_knot out of the two-wave rollout whenever the
+  // knot calc inlined beside it grew).
+  __device__ __forceinline__ bool box_knot(int b, int t) const { return box && haslim && haslim[(int64_t)b * T + t]; }
 
-  __device__ __host__ int64_t knot(int b, int t) const { return (int64_t)b * (T + 1) + t; }
-  __device__ __host__ int64_t run(int b, int t) const { return (int64_t)b * T + t; }
-  __device__ __host__ const double* pblock(int b, int t) const {
+  __device__ __host__ __forceinline__ int64_t knot(int b, int t) const { return (int64_t)b * (T + 1) + t; }
+  __device__ __host__ __forceinline__ int64_t run(int b, int t) const { return (int64_t)b * T + t; }
+  __device__ __host__ __forceinline__ const double* pblock(int b, int t) const {
     return params + knots[t].param_offset + (int64_t)b * knots[t].param_stride;
   }
 };

@@ -723,6 +723,10 @@ int apply_knots(fddp_handle* h, const fddp_knot_desc* knots, const double* param
     return fail(FDDP_ERR_UNSUPPORTED, "the rollout variant chosen does not evaluate the actuation record");
   if (L.has_act && P.var.mb == ktab::MB_S2)  // (... and the spilled-plan calcDiff object)
     return fail(FDDP_ERR_UNSUPPORTED, "the calcDiff variant chosen does not evaluate the actuation record");
+  if (L.has_pris && P.var.fwd == ktab::FWD_MB)  // (MB_PRISMATIC, likewise)
+    return fail(FDDP_ERR_UNSUPPORTED, "the rollout variant chosen does not read prismatic joint records");
+  if (L.has_pris && P.var.mb == ktab::MB_S2)
+    return fail(FDDP_ERR_UNSUPPORTED, "the calcDiff variant chosen does not read prismatic joint records");
   if (L.npar_adapt && !L.fast && std::getenv("FDDP_STAMPS"))  // (diagnostic runs: the rollout's residency)
     std::fprintf(stderr, "[fddp] rollout: %.0f workgroups on %d CUs (LDS %zu B per workgroup)\n", P.var.ls_slots, F.cus,
                  L.fwd_smem);

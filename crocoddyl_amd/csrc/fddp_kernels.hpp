@@ -24,7 +24,7 @@ __device__ inline int64_t block_doubles_dev(int kind, int nx, int nu, const doub
 }
 
 // StateMultibody with a free-flyer root (nx = ndx + 1: x = (p, quat xyzw, q_rest, v)),
-// otherwise a Euclidean state (StateVector, or StateMultibody over revolute joints).
+// otherwise a Euclidean state (StateVector, or StateMultibody over revolute and prismatic joints).
 // diff(x0, x1) / integrate(x, dx) (multibody.hxx:54-91, euclidean.hxx:28-61) over the
 // threads of a workgroup; thread `first` (0 by default) does the free-flyer's SE(3)
 // part, so two differences of one phase can run their logs on different waves. out

@@ -26,6 +26,8 @@
 #define MB_CALC_MOMENTUM 0
 // ... nor one with an actuation record (tau = S u): its calc keeps tau = [0_nun; u] only
 #define MB_ACTUATION 0
+// ... nor one with a prismatic joint record: its predicate stays the free-flyer's
+#define MB_PRISMATIC 0
 #endif
 #include "fast_path.hpp"
 #include "fddp_kernels.hpp"

@@ -13,6 +13,8 @@
 // MB_ACTUATION): its code stays what the headline runs, and the launch plan gives a horizon with
 // such a record the all-LDS plan, whose objects carry them (launch_plan.hpp plan_lds)
 #define MB_ACTUATION 0
+// ... and without the prismatic joint records (MB_PRISMATIC), routed the same way
+#define MB_PRISMATIC 0
 #endif
 // (the rollout objects' MB_BLK_UNIFORM and MB_LANE_OPAQUE, k_fwd.hip, stay off in these
 // objects: on the MB_S2 kernel they cost C5 calcDiff 24.0 -> 24.6 and 24.8 ms; that object

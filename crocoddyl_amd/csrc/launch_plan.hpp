@@ -32,7 +32,8 @@ constexpr int64_t kLdsTwoPerCu = 80 * 1024, kLdsFourPerCu = 40 * 1024;
 struct Overrides {
   int mb_w1 = -1;       // FDDP_MB_W1: 0 / 1 forces the 2- / 1-wave/EU calcDiff build
   int mb_nt = 0;        // FDDP_MB_NT: 128 / 256 / 512 forces the calcDiff workgroup size
-  int mb_spill = -1;    // FDDP_MB_SPILL: 0 forces the all-LDS calcDiff plan
+  int mb_spill = -1;    // FDDP_MB_SPILL: 0 forces the all-LDS calcDiff plan (1: the rule; refused where it
+                        // would spill a horizon that the spilled plan's kernel cannot run, has_pris)
   int fwd_mb_off = 0;   // FDDP_FWD_MB=0: the generic rollout on multibody horizons
   int fwd_mbw = 0;      // FDDP_FWD_MBW: 2 / 3 forces the rollout's waves/EU build
   int bwd_waves = 0;    // FDDP_BWD_WAVES: 1 / 4 / 8 waves per element of the MFMA sweep
@@ -61,6 +62,7 @@ struct LdsPlan {
   bool has_icom = false;        // a knot carries a CostModelImpulseCoM record (no FWD_MB rollout)
   bool has_hmom = false;        // a knot carries a CostModelCentroidalMomentum record (no FWD_MB rollout)
   bool has_act = false;         // a knot carries an actuation record, tau = S u (no FWD_MB rollout, no spilled plan)
+  bool has_pris = false;        // a knot's tree has a prismatic joint record (no FWD_MB rollout, no spilled plan)
   int mb_nj = 0;                // largest multibody tree (dofs)
   int64_t mbw = 0, mbw_fwd = 0, mbd = 0;  // Dev::mbw, mbw_fwd, mbd
   int mbspill = 0, dxv_mbw = 0;           // Dev::mbspill, dxv_mbw
@@ -117,7 +119,7 @@ struct Refusal {
 // dofs, jac costs and contact rows (LDS sizing).
 inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, int nu, Refusal& why, int* nj_out,
                               int* njac_out, int* nc_out, bool* vcols_out = nullptr, int* nu_out = nullptr,
-                              int* nrows_out = nullptr, bool* act_out = nullptr) {
+                              int* nrows_out = nullptr, bool* act_out = nullptr, bool* pris_out = nullptr) {
   using namespace fddp::mb;
   if (avail < FDDP_PARAM_HEADER) return why = "block out of range", -1;
   const double dt = P[0];
@@ -138,14 +140,17 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
   if (impulse && dt != 0.) return why = "impulse blocks carry dt = 0 (no integrator)", -1;
   if ((double)ncost != P[2] || ncost < 0 || ncost > kMaxCosts) return why = "number of costs out of [0, 64]", -1;
   int force_rows = 0;  // rows the contact-force costs read
+  bool pris = false;   // a prismatic joint record
   if (o + (int64_t)kJRec * nb > size) return why = "block too small for its joints", -1;
   for (int i = 0; i < nb; ++i) {
     const double* J = P + o + (int64_t)kJRec * i;
     const int type = (int)J[0], par = (int)J[1];
-    if ((double)type != J[0] || (type != J_REVOLUTE && type != J_FREEFLYER)) return why = "unknown joint type", -1;
+    if ((double)type != J[0] || (type != J_REVOLUTE && type != J_FREEFLYER && type != J_PRISMATIC))
+      return why = "unknown joint type", -1;
     if (type == J_FREEFLYER && (i != 0 || par != -1)) return why = "a free-flyer may only be the root joint", -1;
     if ((double)par != J[1] || par < -1 || par >= i) return why = "joint parents must precede their children", -1;
-    if (type == J_REVOLUTE) {
+    if (type == J_PRISMATIC) pris = true;
+    if (type == J_REVOLUTE || type == J_PRISMATIC) {
       const double an = std::sqrt(J[2] * J[2] + J[3] * J[3] + J[4] * J[4]);
       if (!(std::fabs(an - 1.) < 1e-9)) return why = "joint axes must be unit vectors", -1;
     }
@@ -311,6 +316,7 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
   if (nu_out) *nu_out = std::max(*nu_out, nu);
   if (nrows_out) *nrows_out = std::max(*nrows_out, nrows);
   if (act_out) *act_out = *act_out || act;
+  if (pris_out) *pris_out = *pris_out || pris;
   return size;
 }
 
@@ -349,12 +355,14 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
         const int64_t off = knots[t].param_offset + (int64_t)b * knots[t].param_stride;
         Refusal why;
         MbShape k{0, 0, 0, 0, 0, false, false};
+        bool pris = false;
         const int64_t s1 = mb_block_check(params + off, n_params - off, knots[t].kind, d.nx, knots[t].nu, why, &k.nj,
-                                          &k.njac, &k.nc, &k.vcols, &k.nu, &k.nrows, &k.act);
+                                          &k.njac, &k.nc, &k.vcols, &k.nu, &k.nrows, &k.act, &pris);
         if (s1 < 0 && !refused) refused = why.text;
         if (s1 >= 0 && fddp::mb::has_impulse_com(fddp::mb::parse(params + off))) p.has_icom = true;
         if (s1 >= 0 && fddp::mb::has_momentum(fddp::mb::parse(params + off))) p.has_hmom = true;
         if (s1 >= 0 && k.act) p.has_act = true;
+        if (s1 >= 0 && pris) p.has_pris = true;
         // (a refused block is planned with its size field, as mb_pmax is: the budget below
         // then refuses only what is over it)
         const int64_t own = (int64_t)params[off + 3];
@@ -401,8 +409,9 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
   // (the spill flags themselves from the largest value of every parameter: the spilled
   // arrays must fit their output blocks on every knot)
   // (a horizon with an actuation record never spills: the spilled plan's kernel is built without
-  // the record's phases, MB_ACTUATION in k_mb.hip; every accepted block fits the all-LDS plan)
-  p.mbspill = p.has_mb && !mb_act && ov.mb_spill != 0 && p.mb_all_lds > kLdsTwoPerCu
+  // the record's phases, MB_ACTUATION in k_mb.hip; every accepted block fits the all-LDS plan;
+  // nor does a horizon with a prismatic joint record, MB_PRISMATIC there)
+  p.mbspill = p.has_mb && !mb_act && !p.has_pris && ov.mb_spill != 0 && p.mb_all_lds > kLdsTwoPerCu
                   ? fddp::mb::diff_spill(mb_nj, mb_njac, mb_nc, mb_vcols, mb_nu, mb_nrows, mb_pmax, d.nu_max, mb_act)
                   : 0;
   p.mbd = p.has_mb ? plan_doubles(p.mbspill) : 0;
@@ -446,6 +455,11 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
     p.error = "FDDP_FWD_MBW=3 on a horizon with a centroidal-momentum cost: that rollout build does not evaluate it";
   if (!p.error && p.has_act && ov.fwd_mbw == 3)
     p.error = "FDDP_FWD_MBW=3 on a horizon with an actuation record: that rollout build does not evaluate it";
+  if (!p.error && p.has_pris && ov.fwd_mbw == 3)
+    p.error = "FDDP_FWD_MBW=3 on a horizon with a prismatic joint: that rollout build does not read the joint type";
+  // (asked for by name where the rule would spill: the small plans, which never spill, pass)
+  if (!p.error && p.has_pris && ov.mb_spill > 0 && p.mb_all_lds > kLdsTwoPerCu)
+    p.error = "FDDP_MB_SPILL=1 on a horizon with a prismatic joint: the spilled-plan calcDiff build does not read the joint type";
   return p;
 }
 
@@ -485,10 +499,10 @@ inline VariantPlan plan_variants(const LdsPlan& l, const fddp_dims& d, const Ove
     v.fwd = ktab::FWD_GENERIC;
   } else {
     const bool three = resident_per_cu(f.fwd_api[ktab::FWD_MB], l.fwd_smem, f.fwd_static[ktab::FWD_MB]) >= 3;
-    // (a horizon with an impulse CoM or a centroidal-momentum cost or an actuation record never:
-    // that build's calc has no code for them, MB_CALC_IMPULSE_COM / MB_CALC_MOMENTUM /
-    // MB_ACTUATION; plan_lds refuses the override that would force it)
-    const bool take3 = !l.has_icom && !l.has_hmom && !l.has_act && (ov.fwd_mbw ? ov.fwd_mbw == 3 : (three && d.B > 2 * cus));
+    // (a horizon with an impulse CoM or a centroidal-momentum cost, an actuation record or a
+    // prismatic joint never: that build's calc has no code for them, MB_CALC_IMPULSE_COM /
+    // MB_CALC_MOMENTUM / MB_ACTUATION / MB_PRISMATIC; plan_lds refuses the override that would force it)
+    const bool take3 = !l.has_icom && !l.has_hmom && !l.has_act && !l.has_pris && (ov.fwd_mbw ? ov.fwd_mbw == 3 : (three && d.B > 2 * cus));
     v.fwd = take3 ? ktab::FWD_MB : ktab::FWD_MB2;
   }
   if (!l.fast) v.ls_slots = (double)cus * resident_per_cu(f.fwd_api[v.fwd], l.fwd_smem, f.fwd_static[v.fwd]);

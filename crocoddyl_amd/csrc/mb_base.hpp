@@ -116,6 +116,14 @@ MB_HD __forceinline__ T* mb_lds(T* p) {
 #ifndef MB_ACTUATION
 #define MB_ACTUATION 1
 #endif
+// MB_PRISMATIC (per kernel object): joint records of type J_PRISMATIC are read (Blk::pris, one
+// bit per prismatic dof; dof_prismatic tests it). As MB_ACTUATION: the headline's two kernel
+// objects are built without it, where the predicate is the free-flyer's `ff && d < 3` and parse
+// reads no record type beyond record 0; the launch plan never gives them a horizon with such a
+// record (LdsPlan::has_pris, plan_lds, plan_variants).
+#ifndef MB_PRISMATIC
+#define MB_PRISMATIC 1
+#endif
 
 namespace fddp {
 namespace mb {
@@ -127,7 +135,7 @@ constexpr int kCHdr = 4;          // doubles of a cost record's header
 constexpr int kMaxJacCosts = 8;   // costs with a dense residual Jacobian (frame, CoM, impulse CoM, momentum, free-flyer state)
 constexpr int kMaxNc = 24;        // stacked contact rows (FDDP_KNOT_EULER_CONTACTFWD)
 constexpr int kMbDiffNT = 256;    // threads of the knot-parallel calcDiff workgroup
-enum { J_REVOLUTE = 0, J_FREEFLYER = 1 };
+enum { J_REVOLUTE = 0, J_FREEFLYER = 1, J_PRISMATIC = 2 };
 // Cost record types; contact records (after the costs) use 5 / 6 and the same
 // frame payload as the frame costs, so frame_residual serves both.
 enum {
@@ -162,6 +170,9 @@ struct Blk {
   int nq;   // nv + 1 with a free-flyer root
   int nb;   // joint records (pinocchio joints)
   bool ff;  // record 0 is a free-flyer (dofs 0..5: base twist, body on dof 5)
+#if MB_PRISMATIC
+  Mask pris;  // the prismatic dofs (S = [axis; 0]): a free-flyer's dofs 0..2 and every J_PRISMATIC record's
+#endif
   int ncost;
   const double* g;    // gravity (3)
   const double* arm;  // armature (nv)
@@ -202,6 +213,25 @@ MB_HD __forceinline__ double act_tau(const Blk& b, const double* u, int i) {
   return i < b.nun ? 0. : u[i - b.nun];
 }
 
+#if MB_PRISMATIC
+// One bit per prismatic dof of the nb joint records at J (LDS on the device): a free-flyer's dofs
+// 0..2 and every J_PRISMATIC record's dof. Out of line on the device, as act_row_dot: a knot pays
+// a call per parse, and the kernels' register allocation around it stays what it was (inlined,
+// the loop cost the 128-thread calcDiff kernel, at its 168-VGPR cap, 15 more VGPR spills; out of
+// line 7).
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __attribute__((noinline)) Mask pris_mask(const double* J_, int nb, bool ff) {
+  const double* J = ::fddp::lds_ptr(J_);
+#else
+inline Mask pris_mask(const double* J, int nb, bool ff) {
+#endif
+  Mask m = ff ? Mask(7) : Mask(0);
+  for (int r = ff ? 1 : 0; r < nb; ++r)
+    if ((int)J[kJRec * r] == J_PRISMATIC) m |= Mask(1) << (ff ? r + 5 : r);
+  return m;
+}
+#endif
+
 MB_HD inline Blk parse(const double* P) {
   Blk b;
   b.dt = P[0];
@@ -213,6 +243,9 @@ MB_HD inline Blk parse(const double* P) {
   b.ff = (int)b.J[0] == J_FREEFLYER;
   b.nb = b.ff ? b.nj - 5 : b.nj;
   b.nq = b.ff ? b.nj + 1 : b.nj;
+#if MB_PRISMATIC
+  b.pris = pris_mask(b.J, b.nb, b.ff);
+#endif
   b.C = b.J + (int64_t)kJRec * b.nb;
   const double* e = b.C;
   for (int k = 0; k < b.ncost; ++k) e += (int)e[3];
@@ -266,6 +299,11 @@ __device__ __forceinline__ double mb_uniform(double v) {
   __builtin_memcpy(&v, h, 8);
   return v;
 }
+__device__ __forceinline__ Mask mb_uniform(Mask v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return ((Mask)hi << 32) | lo;
+}
 __device__ __forceinline__ const double* mb_uniform(const double* p) {
   typedef const __attribute__((address_space(3))) double* LdsP;
   const unsigned a = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(LdsP)p);
@@ -281,6 +319,9 @@ MB_HD __forceinline__ Blk parse_uniform(const double* P) {
   b.nq = mb_uniform(b.nq);
   b.nb = mb_uniform(b.nb);
   b.ff = mb_uniform(b.ff);
+#if MB_PRISMATIC
+  b.pris = mb_uniform(b.pris);
+#endif
   b.ncost = mb_uniform(b.ncost);
   b.g = mb_uniform(b.g);
   b.arm = mb_uniform(b.arm);

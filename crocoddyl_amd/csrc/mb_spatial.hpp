@@ -130,11 +130,12 @@ struct JRec {
 // Dof d is one lane. A free-flyer record expands into dofs 0..5 (base twist:
 // linear 0..2 along, angular 3..5 about the base axes) that share one body, whose
 // inertia sits on dof 5; placements compose along 0 -> 1 -> .. -> 5 with the base
-// pose on dof 0 and identities after it. Every other record is one revolute dof.
+// pose on dof 0 and identities after it. Every other record is one dof, revolute (about its
+// axis) or prismatic (along it).
 MB_HD __forceinline__ int rec_of(const Blk& b, int d) { return b.ff ? (d < 6 ? 0 : d - 5) : d; }
 // the dof that carries record r's body (and its frames)
 MB_HD __forceinline__ int dof_of_rec(const Blk& b, int r) { return b.ff ? (r == 0 ? 5 : r + 5) : r; }
-// configuration index of a revolute dof
+// configuration index of a one-dof joint (an angle or a length)
 MB_HD __forceinline__ int qof(const Blk& b, int d) { return b.ff ? d + 1 : d; }
 // the dof carrying the parent body (-1: universe)
 MB_HD __forceinline__ int body_parent(const Blk& b, int d) {
@@ -153,7 +154,11 @@ MB_HD inline Mask anc_mask(const Blk& b, int d) {
 }
 MB_HD __forceinline__ bool carries_body(const Blk& b, int d) { return !(b.ff && d < 5); }
 // joint-frame axis of dof d; prismatic: translation along it (free-flyer 0..2)
+#if MB_PRISMATIC
+MB_HD __forceinline__ bool dof_prismatic(const Blk& b, int d) { return (b.pris >> d) & 1ull; }
+#else
 MB_HD __forceinline__ bool dof_prismatic(const Blk& b, int d) { return b.ff && d < 3; }
+#endif
 MB_HD __forceinline__ void dof_axis(const Blk& b, int d, double* ax) {
   if (b.ff && d < 6) {
     ax[0] = d % 3 == 0 ? 1. : 0.;

@@ -95,8 +95,19 @@ MB_HD inline void w_joint_local(const Blk& b, const WVals& W, const double* q, i
     double ax[3], Rpl[9];
     for (int e = 0; e < 3; ++e) ax[e] = J.axis()[e];
     for (int e = 0; e < 9; ++e) Rpl[e] = J.Rpl()[e];
-    joint_rotation(Rpl, ax, q[qof(b, i)], R);
-    for (int e = 0; e < 3; ++e) p[e] = J.ppl()[e];
+#if MB_PRISMATIC
+    if (dof_prismatic(b, i)) {  // liMi = (Rpl, ppl + Rpl axis q)
+      double t[3];
+      matvec3(Rpl, ax, t);
+      const double qi = q[qof(b, i)];
+      for (int e = 0; e < 9; ++e) R[e] = Rpl[e];
+      for (int e = 0; e < 3; ++e) p[e] = J.ppl()[e] + t[e] * qi;
+    } else
+#endif
+    {
+      joint_rotation(Rpl, ax, q[qof(b, i)], R);
+      for (int e = 0; e < 3; ++e) p[e] = J.ppl()[e];
+    }
   }
   for (int e = 0; e < 9; ++e) {
     W.R(i)[e] = R[e];

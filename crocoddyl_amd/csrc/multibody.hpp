@@ -1,7 +1,7 @@
 // Multibody knots on the device: IntegratedActionModelEuler ∘
 // DifferentialAction{Free,Contact}FwdDynamics and ActionModelImpulseFwdDynamics
 // (CostModelSum of State / Control / FramePlacement / FrameTranslation / CoMPosition /
-// ContactForce costs) over a kinematic tree of revolute joints below either the
+// ContactForce costs) over a kinematic tree of revolute and prismatic joints below either the
 // universe or a free-flyer root (StateMultibody on SE(3) x R^n).
 //
 // Reference: include/crocoddyl/core/integrator/euler.hxx:41-131,
@@ -13,7 +13,10 @@
 //   * forward dynamics: a = (M + diag(armature))^-1 (tau - nle), with RNEA and the
 //     composite-rigid-body algorithm in world coordinates, where every recursion is
 //     an ancestor / subtree sum evaluated one dof per lane (a free-flyer is six dofs
-//     that share one body), and the solve by Gauss-Jordan with one column per lane.
+//     that share one body; a prismatic joint is a dof with S = [oR axis; 0] and the local
+//     placement (Rpl, ppl + Rpl axis q), as the free-flyer's first three dofs: nothing below
+//     the motion subspaces knows the joint type), and the solve by Gauss-Jordan with one
+//     column per lane.
 //     (The reference's default path is ABA, the same function.)
 //   * derivatives: the world-frame analytic RNEA derivatives, one lane per tangent
 //     direction (q_j or v_j): every world quantity of the subtree moved by q_j is

@@ -23,7 +23,7 @@ Reference API mirrored:
                                                 multibody/actions/free-fwddyn.hxx:24-160
 Pinocchio is not available offline, so ``RobotModel`` stands in for
 ``pinocchio.Model`` over the subset the device covers: a kinematic tree of
-revolute joints (any unit axis) below either the universe or a free-flyer root
+revolute and prismatic joints (any unit axis) below either the universe or a free-flyer root
 (JointModelFreeFlyer: q = (p, quat xyzw), v = base twist), with joint
 placements, body inertias, operational frames and gravity. Joint and frame
 indices follow Pinocchio's (joint 0 / frame 0 = universe).
@@ -34,7 +34,7 @@ from . import _abi
 from .models import _ControlLimits
 
 JOINT_REC = 27
-JOINT_REVOLUTE, JOINT_FREEFLYER = 0, 1
+JOINT_REVOLUTE, JOINT_FREEFLYER, JOINT_PRISMATIC = 0, 1, 2
 COST_HDR = 4
 COST_STATE, COST_CONTROL, COST_FRAME_PLACEMENT, COST_FRAME_TRANSLATION = 1, 2, 3, 4
 CONTACT_3D, CONTACT_6D = 5, 6
@@ -134,9 +134,33 @@ def JointModelRZ():
     return JointModelRevoluteUnaligned((0.0, 0.0, 1.0))
 
 
+class JointModelPrismaticUnaligned:
+    """pinocchio::JointModelPrismaticUnaligned(axis): q is a length along the axis."""
+    nq, nv = 1, 1
+
+    def __init__(self, *axis):
+        ax = np.array(axis[0] if len(axis) == 1 else axis, np.float64).reshape(3)
+        n = np.linalg.norm(ax)
+        if n == 0:
+            raise ValueError("Invalid argument: zero joint axis")
+        self.axis = ax / n
+
+
+def JointModelPX():
+    return JointModelPrismaticUnaligned((1.0, 0.0, 0.0))
+
+
+def JointModelPY():
+    return JointModelPrismaticUnaligned((0.0, 1.0, 0.0))
+
+
+def JointModelPZ():
+    return JointModelPrismaticUnaligned((0.0, 0.0, 1.0))
+
+
 class RobotModel:
-    """Stand-in for pinocchio.Model: revolute trees, optionally below a
-    free-flyer root (the only joint allowed to be a JointModelFreeFlyer)."""
+    """Stand-in for pinocchio.Model: trees of revolute and prismatic joints, optionally
+    below a free-flyer root (the only joint allowed to be a JointModelFreeFlyer)."""
 
     def __init__(self, root_joint=None):
         self.names = ["universe"]
@@ -180,9 +204,10 @@ class RobotModel:
 
     def addJoint(self, parent_id, joint, placement, name):
         """pinocchio Model::addJoint(parent, joint_model, placement, name):
-        ``joint`` is a JointModelFreeFlyer / JointModelRevoluteUnaligned (or a
-        bare axis, a revolute joint about it), placed at ``placement`` in the
-        parent joint's frame. Returns its index."""
+        ``joint`` is a JointModelFreeFlyer / JointModelRevoluteUnaligned /
+        JointModelPrismaticUnaligned (or a bare axis of three numbers, a revolute joint
+        about it), placed at ``placement`` in the parent joint's frame. Any other object
+        is refused. Returns its index."""
         parent_id = int(parent_id)
         if not 0 <= parent_id < self.njoints:
             raise ValueError("Invalid argument: unknown parent joint")
@@ -190,9 +215,14 @@ class RobotModel:
             if self.njoints != 1 or parent_id != 0:
                 raise ValueError("Invalid argument: the device path takes a free-flyer as the root joint only")
             kind, ax, nvj = JOINT_FREEFLYER, np.zeros(3), 6
+        elif isinstance(joint, JointModelPrismaticUnaligned):
+            kind, ax, nvj = JOINT_PRISMATIC, joint.axis, 1
         else:
             if not isinstance(joint, JointModelRevoluteUnaligned):
-                joint = JointModelRevoluteUnaligned(joint)
+                if not isinstance(joint, (tuple, list, np.ndarray)) or np.size(joint) != 3:
+                    raise ValueError(f"Invalid argument: unknown joint model {type(joint).__name__} (the device path "
+                                     "covers free-flyer, revolute and prismatic joints)")
+                joint = JointModelRevoluteUnaligned(np.asarray(joint, np.float64))
             kind, ax, nvj = JOINT_REVOLUTE, joint.axis, 1
         if self.nv + nvj > MAX_DOFS:
             raise ValueError(f"Invalid argument: the device path holds at most {MAX_DOFS} dofs")
@@ -206,8 +236,8 @@ class RobotModel:
         return self.njoints - 1
 
     def setJointLimits(self, joint_id, lower, upper, velocity):
-        """Position / velocity limits of a revolute joint (the URDF <limit> that
-        pinocchio stores in lower/upperPositionLimit, velocityLimit)."""
+        """Position / velocity limits of a revolute (rad, rad/s) or prismatic (m, m/s) joint
+        (the URDF <limit> that pinocchio stores in lower/upperPositionLimit, velocityLimit)."""
         self._limits[int(joint_id)] = (float(lower), float(upper), float(velocity))
 
     @property
@@ -227,8 +257,8 @@ class RobotModel:
         return out
 
     def setEffortLimit(self, joint_id, effort):
-        """Torque limit of a revolute joint (the URDF <limit effort> that pinocchio
-        stores in Model::effortLimit)."""
+        """Torque limit of a revolute joint, force limit (N) of a prismatic one (the URDF
+        <limit effort> that pinocchio stores in Model::effortLimit)."""
         self._effort[int(joint_id)] = float(effort)
 
     @property
@@ -301,6 +331,8 @@ class RobotModel:
             iq = self.idx_q(j)
             if self.kinds[j] == JOINT_FREEFLYER:
                 Mj = SE3(_quat_to_R(q[iq + 3:iq + 7]), q[iq:iq + 3])
+            elif self.kinds[j] == JOINT_PRISMATIC:
+                Mj = SE3(None, self.axes[j] * q[iq])
             else:
                 Mj = SE3(_rot_axis(self.axes[j], q[iq]))
             out.append(out[self.parents[j]] * (self.jointPlacements[j] * Mj))
@@ -328,6 +360,9 @@ class RobotModel:
                     ax = R[:, k % 3]
                     S.append(np.concatenate([ax, np.zeros(3)]) if k < 3 else np.concatenate([np.cross(p, ax), ax]))
                     owner.append(j)
+            elif self.kinds[j] == JOINT_PRISMATIC:
+                S.append(np.concatenate([R @ self.axes[j], np.zeros(3)]))
+                owner.append(j)
             else:
                 w = R @ self.axes[j]
                 S.append(np.concatenate([np.cross(p, w), w]))
@@ -487,9 +522,15 @@ def sample_talos_arm():
     return m
 
 
-def sample_tree(nj, seed=0, branching=True, freeflyer=False):
+def sample_tree(nj, seed=0, branching=True, freeflyer=False, prismatic=()):
     """Random kinematic tree (tests): random axes, placements and inertias; with
-    ``freeflyer`` the nj revolute joints hang below a free-flyer base (joint 1)."""
+    ``freeflyer`` the nj one-dof joints hang below a free-flyer base (joint 1).
+    ``prismatic``: which of the nj joints (0-based, in the order they are added) slide
+    along their axis instead of turning about it; the random draws do not depend on it,
+    so the default tree is what it always was."""
+    prismatic = {int(k) for k in prismatic}
+    if any(not 0 <= k < nj for k in prismatic):
+        raise ValueError("Invalid argument: prismatic joint index out of range")
     rng = np.random.default_rng(seed)
     m = RobotModel(JointModelFreeFlyer() if freeflyer else None)
     if freeflyer:
@@ -504,7 +545,8 @@ def sample_tree(nj, seed=0, branching=True, freeflyer=False):
         t = np.linalg.norm(ang)
         K = np.array([[0, -ang[2], ang[1]], [ang[2], 0, -ang[0]], [-ang[1], ang[0], 0]])
         R = np.eye(3) + np.sin(t) / t * K + (1 - np.cos(t)) / t ** 2 * K @ K
-        jid = m.addJoint(parent, ax, SE3(R, rng.uniform(-0.3, 0.3, 3)), f"j{j}")
+        joint = JointModelPrismaticUnaligned(ax) if j - first in prismatic else ax
+        jid = m.addJoint(parent, joint, SE3(R, rng.uniform(-0.3, 0.3, 3)), f"j{j}")
         A = rng.normal(size=(3, 3)) * 0.05
         m.appendBodyToJoint(jid, Inertia(rng.uniform(0.3, 3.0), rng.uniform(-0.1, 0.1, 3),
                                          A @ A.T + 0.01 * np.eye(3)))
@@ -515,7 +557,7 @@ def sample_tree(nj, seed=0, branching=True, freeflyer=False):
 class StateMultibody:
     """StateMultibody (multibody.hxx:14-240): x = (q, v), nx = nq + nv,
     ndx = 2 nv; diff / integrate are pinocchio::difference / integrate
-    (multibody.hxx:54-91): Euclidean on revolute joints, SE(3) (M0^-1 M1 ->
+    (multibody.hxx:54-91): Euclidean on revolute and prismatic joints, SE(3) (M0^-1 M1 ->
     log6, M exp6(dq)) on a free-flyer root."""
 
     def __init__(self, model):
@@ -582,7 +624,7 @@ class ActuationModelFull:
 class ActuationModelFloatingBase:
     """ActuationModelFloatingBase (actuations/floating-base.hpp:29-61): the
     root joint's dofs are unactuated, tau = [0; u], nu = nv - nv(joint 1)
-    (6 for a free-flyer root, 1 for a revolute one)."""
+    (6 for a free-flyer root, 1 for a revolute or prismatic one)."""
 
     def __init__(self, state):
         self.state = state

@@ -31,6 +31,9 @@ calcDiff (contact-fwddyn.hxx:107-160, euler.hxx:83-131, cost-sum.hxx:122-160), a
   costs: residual Jacobians (frame: Jlog6 x frame Jacobian 72 n + 42 d) and the
     Gauss-Newton products R^T diag(w h) R over each cost's columns c: nr c (c + 1)
     (symmetric half), gradients 2 nr c; state / control costs 4 per entry.
+A prismatic dof has no joint rotation and a three-entry motion subspace [axis; 0]: its
+forward transforms cost a translation (c_X -> 24), S.f three products (c_dot -> 5); the RNEA
+and CRBA terms per dof are priced 350 -> 320 and 236 -> 215 for it.
 Impulse knots (impulse-fwddyn.hxx) take the calc's and calcDiff's contact terms with
 the impulse rows; free-dynamics knots nc = 0. The impulse costs: the multiplier rows as
 the contact costs' (over the x columns), CostModelImpulseCoM 10 n for Jcom (v+ - v) and,
@@ -158,8 +161,10 @@ def knot_flops(model):
         frames = ([dam.contacts.contacts[k].contact for k in dam.contacts.active]
                   if isinstance(dam, mb.DifferentialActionModelContactFwdDynamics) else [])
     fdepth = sum(_frame_depth(robot, f.frame if imp else f._ref.id) for f in frames)
-    rnea = 350 * n
-    crba = 236 * n + 53 * sd
+    npris = sum(1 for k in robot.kinds[1:] if k == mb.JOINT_PRISMATIC)
+    # (a prismatic dof: no rotation in its transform, S.f over three entries)
+    rnea = 350 * n - 30 * npris
+    crba = 236 * n - 21 * npris + 53 * sd
     jac = C_X * fdepth + 100 * len(frames)
     chol = sd2 + 2 * sd
     solve = 4 * sd + n

@@ -14,10 +14,14 @@ reference configurations), as ``crocoddyl_amd.multibody.RobotModel`` objects.
   sample_solo12(): free-flyer + 4 legs x 3 (HAA, HFE, KFE): nq = 19, nv = 18 (C4)
   sample_quadrotor(arm_joints=0): a free-flyer base body, optionally with a short revolute
                    chain below it (nv = 6 + arm_joints); quadrotor_tau_f(): the rotor map
+  sample_cartpole(): a prismatic cart along x carrying a revolute pole about y (nv = 2)
+  sample_hopper(legs=2): a free-flyer body on telescopic legs, a revolute hip and a prismatic
+                   shank each (nv = 6 + 2 legs)
 """
 import numpy as np
 
-from .multibody import (SE3, Inertia, JointModelFreeFlyer, JointModelRevoluteUnaligned, RobotModel)
+from .multibody import (SE3, Inertia, JointModelFreeFlyer, JointModelPrismaticUnaligned, JointModelRevoluteUnaligned,
+                        RobotModel)
 
 _X, _Y, _Z = (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0)
 
@@ -150,3 +154,51 @@ def quadrotor_tau_f(d=0.1525, cf=6.6e-5, cm=1e-6):
     r = cm / cf
     return np.array([[0.0, 0.0, 0.0, 0.0], [0.0, 0.0, 0.0, 0.0], [1.0, 1.0, 1.0, 1.0], [0.0, d, 0.0, -d],
                      [-d, 0.0, d, 0.0], [-r, r, -r, r]])
+
+
+def sample_cartpole(cart_mass=1.0, pole_mass=0.3, pole_length=0.8):
+    """The cart-pole of the reference's examples/cartpole_swing_up.py as a tree: ``cart_joint``
+    slides along x (q0 in metres), ``pole_joint`` turns about y below it with the pole's point
+    mass at -pole_length z (q1 = 0: the pole hangs). Frames: one per joint and ``pole_tip`` at
+    the mass. Only the cart is driven: ActuationModelLinear with S = [1, 0]^T."""
+    m = RobotModel()
+    cart = m.addJoint(0, JointModelPrismaticUnaligned(_X), SE3(), "cart_joint")
+    _body(m, cart, cart_mass, (0.0, 0.0, 0.0), (0.02, 0.02, 0.02))
+    m.addFrame("cart_joint", cart)
+    pole = m.addJoint(cart, JointModelRevoluteUnaligned(_Y), SE3(), "pole_joint")
+    _body(m, pole, pole_mass, (0.0, 0.0, -pole_length), (0.0, 0.0, 0.0))
+    m.addFrame("pole_joint", pole)
+    m.addFrame("pole_tip", pole, SE3(np.eye(3), (0.0, 0.0, -pole_length)))
+    return m
+
+
+def sample_hopper(legs=2):
+    """A hopper on telescopic legs: a free-flyer body (frame ``base_link``), and per leg a
+    revolute hip about y (``leg<k>_hip``) and a prismatic shank along the leg's -z
+    (``leg<k>_shank``, q in metres, 0: the leg at its nominal length) with a ``leg<k>_foot`` frame
+    at the shank's end. The legs are spread along y. nv = 6 + 2 legs.
+    referenceConfigurations["standing"]: the feet on the ground, the legs slightly splayed."""
+    if legs < 1:
+        raise ValueError("Invalid argument: a hopper needs at least one leg")
+    m = RobotModel(JointModelFreeFlyer())
+    _body(m, 1, 4.0, (0.0, 0.0, 0.02), (0.06, 0.05, 0.07))
+    m.addFrame("root_joint", 1)
+    m.addFrame("base_link", 1)
+    q = [0.0, 0.0, 0.58, 0.0, 0.0, 0.0, 1.0]
+    for k in range(legs):
+        y = 0.0 if legs == 1 else 0.12 * (2.0 * k / (legs - 1) - 1.0)
+        hip = m.addJoint(1, JointModelRevoluteUnaligned(_Y), SE3(np.eye(3), (0.0, y, -0.05)), f"leg{k}_hip")
+        _body(m, hip, 0.8, (0.0, 0.0, -0.12), (0.006, 0.006, 0.001))
+        m.addFrame(f"leg{k}_hip", hip)
+        shank = m.addJoint(hip, JointModelPrismaticUnaligned((0.0, 0.0, -1.0)), SE3(np.eye(3), (0.0, 0.0, -0.25)),
+                           f"leg{k}_shank")
+        _body(m, shank, 0.4, (0.0, 0.0, -0.15), (0.004, 0.004, 0.0005))
+        m.addFrame(f"leg{k}_shank", shank)
+        m.addFrame(f"leg{k}_foot", shank, SE3(np.eye(3), (0.0, 0.0, -0.3)))
+        m.setJointLimits(hip, -1.2, 1.2, 10.0)
+        m.setJointLimits(shank, -0.15, 0.15, 3.0)  # metres, m/s
+        m.setEffortLimit(hip, 40.0)
+        m.setEffortLimit(shank, 200.0)  # newtons
+        q += [0.1 if k % 2 == 0 else -0.1, -0.02]
+    m.referenceConfigurations["standing"] = np.array(q)
+    return m

@@ -9,7 +9,8 @@
 // Reference classes mirrored (same names, constructor arguments and defaults):
 //   pinocchio::Model subset: Model (addJoint, appendBodyToJoint, addFrame, getFrameId,
 //     getJointId, nq, nv, gravity, referenceConfigurations, limits), SE3, Inertia,
-//     JointModelFreeFlyer, JointModelRevoluteUnaligned / RX / RY / RZ
+//     JointModelFreeFlyer, JointModelRevoluteUnaligned / RX / RY / RZ,
+//     JointModelPrismaticUnaligned / PX / PY / PZ
 //   StateMultibody                            multibody/states/multibody.hxx:14-240
 //   ActuationModelFull / ActuationModelFloatingBase   multibody/actuations/{full,floating-base}.hpp
 //   ActuationModelMultiCopterBase                     multibody/actuations/multicopter-base.hpp
@@ -47,7 +48,7 @@ namespace crocoddyl_amd {
 
 // record type codes of the multibody blocks (include/fddp_hip.h)
 enum { kJointRec = 27, kCostHdr = 4, kMaxContactRows = 24, kMaxDofs = 64 };
-enum { JOINT_REVOLUTE = 0, JOINT_FREEFLYER = 1 };
+enum { JOINT_REVOLUTE = 0, JOINT_FREEFLYER = 1, JOINT_PRISMATIC = 2 };
 enum { COST_STATE = 1, COST_CONTROL = 2, COST_FRAME_PLACEMENT = 3, COST_FRAME_TRANSLATION = 4, CONTACT_3D = 5,
        CONTACT_6D = 6, COST_CONTACT_FORCE = 7, COST_COM_POSITION = 8, COST_FRICTION_CONE = 9,
        COST_FRAME_VELOCITY = 10, COST_COP_POSITION = 11, COST_FRAME_ROTATION = 12, COST_IMPULSE_COM = 13,
@@ -182,6 +183,19 @@ struct JointModelRevoluteUnaligned {
 inline JointModelRevoluteUnaligned JointModelRX() { return JointModelRevoluteUnaligned(1., 0., 0.); }
 inline JointModelRevoluteUnaligned JointModelRY() { return JointModelRevoluteUnaligned(0., 1., 0.); }
 inline JointModelRevoluteUnaligned JointModelRZ() { return JointModelRevoluteUnaligned(0., 0., 1.); }
+// pinocchio::JointModelPrismaticUnaligned(axis): q is a length along the axis
+struct JointModelPrismaticUnaligned {
+  Vec3 axis;
+  explicit JointModelPrismaticUnaligned(const Vec3& a) {
+    const double n = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    if (n == 0.) throw Exception("Invalid argument: zero joint axis");
+    axis = a / n;
+  }
+  JointModelPrismaticUnaligned(double x, double y, double z) : JointModelPrismaticUnaligned(Vec3(x, y, z)) {}
+};
+inline JointModelPrismaticUnaligned JointModelPX() { return JointModelPrismaticUnaligned(1., 0., 0.); }
+inline JointModelPrismaticUnaligned JointModelPY() { return JointModelPrismaticUnaligned(0., 1., 0.); }
+inline JointModelPrismaticUnaligned JointModelPZ() { return JointModelPrismaticUnaligned(0., 0., 1.); }
 
 inline Mat3 skew(const Vec3& w) {
   Mat3 K;
@@ -215,8 +229,8 @@ inline Mat3 quat_to_R(double x, double y, double z, double w) {
   return R;
 }
 
-// pinocchio::Model stand-in over the subset the device covers: revolute trees,
-// optionally below a free-flyer root. Joint / frame 0 = universe, as in Pinocchio.
+// pinocchio::Model stand-in over the subset the device covers: trees of revolute and
+// prismatic joints, optionally below a free-flyer root. Joint / frame 0 = universe, as in Pinocchio.
 // From a real pinocchio::Model: one joint record per joint from
 // model.parents, model.jointPlacements, model.inertias and the joint's axis;
 // frames from model.frames (name, parent joint, placement).
@@ -272,6 +286,9 @@ class Model {
   int addJoint(int parent, const JointModelRevoluteUnaligned& j, const SE3& placement, const std::string& name) {
     return add(parent, JOINT_REVOLUTE, j.axis, placement, name, 1);
   }
+  int addJoint(int parent, const JointModelPrismaticUnaligned& j, const SE3& placement, const std::string& name) {
+    return add(parent, JOINT_PRISMATIC, j.axis, placement, name, 1);
+  }
   void appendBodyToJoint(int joint, const Inertia& I, const SE3& placement = SE3()) {
     inertias.at(joint) = inertias.at(joint) + I.se3Action(placement);
   }
@@ -294,7 +311,7 @@ class Model {
       if (names[i] == name) return (int)i;
     return njoints();
   }
-  // URDF <limit> of a revolute joint (lower/upperPositionLimit, velocityLimit)
+  // URDF <limit> of a revolute (rad, rad/s) or prismatic (m, m/s) joint (lower/upperPositionLimit, velocityLimit)
   void setJointLimits(int joint, double lower, double upper, double velocity) {
     limits_[joint] = {lower, upper, velocity};
   }
@@ -322,6 +339,8 @@ class Model {
       SE3 Mj;
       if (kinds[j] == JOINT_FREEFLYER)
         Mj = SE3(quat_to_R(q[iq + 3], q[iq + 4], q[iq + 5], q[iq + 6]), Vec3(q[iq], q[iq + 1], q[iq + 2]));
+      else if (kinds[j] == JOINT_PRISMATIC)
+        Mj = SE3(Mat3::Identity(), axes[j] * q[iq]);
       else
         Mj = SE3(rot_axis(axes[j], q[iq]), Vec3());
       out[j] = out[parents[j]] * (jointPlacements[j] * Mj);

@@ -73,17 +73,22 @@ int fddp_abi_version(void);
  * DifferentialActionModelFreeFwdDynamics (multibody/actions/free-fwddyn.hxx:44-118)
  * with ActuationModelFull (tau = u) and a CostModelSum (cost-sum.hxx:89-160) over
  * a kinematic tree (StateMultibody, multibody/states/multibody.hxx:54-240): revolute
- * joints, optionally below a free-flyer root (JointModelFreeFlyer: q = (p, quat
+ * and prismatic joints, optionally below a free-flyer root (JointModelFreeFlyer: q = (p, quat
  * x y z w), v = body twist (linear, angular); nq = nv + 1). nx = nq + nv,
  * ndx = 2 nv; nu = nv (no free-flyer). Variable-size block:
  *   header [dt, nv, ncost, size (doubles, header included)]
  *   gravity(3)  armature(nv)
  *   one 27-double record per joint (a free-flyer root is ONE record for its 6
  *   dofs), parents before children (Pinocchio order):
- *     [type (0 revolute, 1 free-flyer), parent record (-1 = universe), axis(3,
- *     unit, joint frame; unused for the free-flyer), placement in the parent
+ *     [type (0 revolute, 1 free-flyer, 2 prismatic), parent record (-1 = universe),
+ *     axis(3, unit, joint frame: the rotation axis of a revolute joint, the translation
+ *     axis of a prismatic one; unused for the free-flyer), placement in the parent
  *     joint frame R(9, column-major) p(3), body mass, CoM(3, joint frame),
  *     rotational inertia about the CoM (Ixx Iyy Izz Ixy Ixz Iyz)]
+ *     Type 2 is pinocchio's JointModelPrismaticUnaligned / PX / PY / PZ: nq = nv = 1, q a
+ *     length, joint placement (I, axis q), motion subspace [axis; 0]; it may stand wherever
+ *     a revolute joint may (below the universe, a free-flyer, a revolute or another
+ *     prismatic joint), in all three multibody knot kinds. A free-flyer is the root only.
  *   ncost cost records in name order (CostModelSum's std::map), each
  *     [type, weight, activation kind, size (doubles, record header included)]
  *     then the payload, then the activation parameters:
