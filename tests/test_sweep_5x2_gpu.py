@@ -21,14 +21,17 @@ B = 3 with per-element matrices. The bar is the project's 1e-8 element-wise with
 on these well-conditioned shapes the oracle's own spread under one-ulp parameter noise is
 below 2e-14 on every quantity (on the trees the floors are computed, as the gaits' are).
 
-The `else` arm of chol_inv_blocked2 (1 <= mu <= 16 on this plan) has no case, nor has any
-knot with 0 < mu < nu_max: it needs an all-multibody horizon with nu_max >= 17 and an
-under-actuated knot, which no builder makes (a dense mixed-nu horizon runs the generic
-sweep). Found by the (78, 32) case: fddp_create refused that shape."""
+The `else` arm of chol_inv_blocked2 (1 <= mu <= 16 on this plan) and knots with 0 < mu < nu_max
+need an all-multibody horizon with nu_max >= 17 and an under-actuated knot (a dense mixed-nu
+horizon runs the generic sweep): the actuation records of tests/mixed_nu_cases.py make them, and
+tests/test_mixed_nu_gpu.py runs them against the numpy reference (the C++ oracle does not know the
+record); the last test here holds their mu transitions next to this module's shapes. Found by the
+(78, 32) case: fddp_create refused that shape."""
 import numpy as np
 import pytest
 
 import helpers
+import mixed_nu_cases as mc
 import oracle_lib
 import variant_cases as vc
 from crocoddyl_amd import _abi, synthetic
@@ -240,6 +243,17 @@ def test_the_528_cases_cover_the_plan():
     assert {1, 2, 15, 16} <= {m - 16 for _, m in dense}  # the second Cholesky block
     mixed = mixed_tree_setup()[0]
     assert 0 in [k[1] for k in mixed["knots"]][:T]  # a knot with mu = 0
+    # knots with 0 < mu < nu_max (tests/mixed_nu_cases.py, run by tests/test_mixed_nu_gpu.py on this code): the
+    # (mu of knot t + 1, mu of knot t) pairs the sweep meets cover both arms of chol_inv_blocked2 and mu = 0 in
+    # every order, mu = 1 and 16, m2 = 1, 15 and 16, and a knot 0 below nu_max; every one on an even n (no
+    # multibody tree has an odd ndx), at both ends of the plan's range
+    nus = {key: mc.problem(key)["nus"] for key in mc.BIG}
+    pairs = {(mc.arm_528(a), mc.arm_528(b)) for v in nus.values() for a, b in mc.transitions(v)}
+    assert pairs == {(a, b) for a in ("two", "else", "none") for b in ("two", "else", "none")} - {("none", "none")}
+    mus = {mu for v in nus.values() for mu in v}
+    assert {0, 1, 16} <= mus and {1, 15, 16} <= {mu - 16 for mu in mus if mu > 16}
+    assert all(any(0 < mu < max(v) for mu in v) for v in nus.values()) and any(v[0] < max(v) for v in nus.values())
+    assert {mc.problem(key)["dims"].ndx for key in mc.BIG} == {66, 78}
     # every regularisation and box shape is one of the plan's, each parity once
     assert all(65 <= n <= 78 and 17 <= m <= 32 for n, m in REG_SHAPES + BOX_SHAPES + FEASIBLE_TOO)
     assert {n % 2 for n, _ in REG_SHAPES} == {0, 1} == {n % 2 for n, _ in BOX_SHAPES}
