@@ -739,7 +739,9 @@ __global__ __launch_bounds__(NT) void backward_kernel(Dev D, Prm prm, int mode) 
 // other trajectory buffer (accepted by flipping cur), slots > 0 the parallel copies.
 struct TrialOut {
   double *xs, *us, *xnext, *kcost, *dvp;
-  __device__ TrialOut(const Dev& D, int o, int slot) {
+  // (always inlined, as the Dev accessors: out of line it takes the address of the kernel's by-value
+  // Dev argument, and the whole struct then lives in scratch)
+  __device__ __forceinline__ TrialOut(const Dev& D, int o, int slot) {
     if (slot == 0) {
       xs = D.xs[o], us = D.us[o], xnext = D.xnext[o], kcost = D.kcost[o], dvp = D.dvp;
     } else {

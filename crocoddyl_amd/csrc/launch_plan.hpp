@@ -61,7 +61,7 @@ struct LdsPlan {
   bool all_mb = false;          // every knot is a multibody knot
   bool has_icom = false;        // a knot carries a CostModelImpulseCoM record (no FWD_MB rollout)
   bool has_hmom = false;        // a knot carries a CostModelCentroidalMomentum record (no FWD_MB rollout)
-  bool has_act = false;         // a knot carries an actuation record, tau = S u (no FWD_MB rollout, no spilled plan)
+  bool has_act = false;         // a knot carries an actuation record, tau = S u or S s(u) (no FWD_MB rollout, no spilled plan)
   bool has_pris = false;        // a knot's tree has a prismatic joint record (no FWD_MB rollout, no spilled plan)
   int mb_nj = 0;                // largest multibody tree (dofs)
   int64_t mbw = 0, mbw_fwd = 0, mbd = 0;  // Dev::mbw, mbw_fwd, mbd
@@ -119,7 +119,8 @@ struct Refusal {
 // dofs, jac costs and contact rows (LDS sizing).
 inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, int nu, Refusal& why, int* nj_out,
                               int* njac_out, int* nc_out, bool* vcols_out = nullptr, int* nu_out = nullptr,
-                              int* nrows_out = nullptr, bool* act_out = nullptr, bool* pris_out = nullptr) {
+                              int* nrows_out = nullptr, bool* act_out = nullptr, bool* pris_out = nullptr,
+                              bool* sat_out = nullptr) {
   using namespace fddp::mb;
   if (avail < FDDP_PARAM_HEADER) return why = "block out of range", -1;
   const double dt = P[0];
@@ -234,6 +235,7 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
   }
   int nc = 0;
   bool act = false;  // flag bit 4: an actuation record after the contacts
+  bool sat = false;  // ... whose header slot 1 is SQ_SMOOTH_SAT: tau = S s(u)
   std::vector<std::pair<int, int>> crow;  // (row0, rows) of every contact record
   if (contact || impulse) {  // [nun | r_coeff, damping, ncontact, 0 | 2 | 4 | 6 (contact), 1 | 3 (impulse)] + records
     if (o + 4 > size) return why = "contact section out of range", -1;
@@ -277,14 +279,29 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
     }
     if (nc > kMaxNc) return why = "more than 24 contact rows in one knot", -1;
     if (act) {  // [20, 0, 0, 4 + nv nu] + S (nv x nu, column-major): tau = S u
+                // [20, 1, 0, 4 + nv nu + 3 nu] + S + lb(nu) + ub(nu) + a(nu): tau = S s(u), smooth-sat
       if (o + kCHdr > size) return why = "block ends before its actuation record", -1;
       const double* A = P + o;
       if (A[0] != (double)C_ACTUATION) return why = "actuation record of the wrong type", -1;
-      const int64_t want = kCHdr + (int64_t)nj * nu;
+      if (A[1] != (double)SQ_NONE && A[1] != (double)SQ_SMOOTH_SAT)
+        return why = "actuation record with an unknown squashing kind", -1;
+      sat = A[1] == (double)SQ_SMOOTH_SAT;
+      const int64_t want = kCHdr + (int64_t)nj * nu + (sat ? 3 * (int64_t)nu : 0);
       if (A[3] != (double)want) return why = "actuation record of the wrong size", -1;
       if (o + want > size) return why = "block ends before its actuation record", -1;
       for (int64_t e = 0; e < (int64_t)nj * nu; ++e)
         if (!std::isfinite(A[kCHdr + e])) return why = "non-finite entry in the actuation matrix", -1;
+      if (sat) {
+        const double* lb = A + kCHdr + (int64_t)nj * nu;
+        const double *ub = lb + nu, *a = ub + nu;
+        for (int c = 0; c < 3 * nu; ++c)
+          if (!std::isfinite(lb[c])) return why = "non-finite squashing bound or smoothing term", -1;
+        for (int c = 0; c < nu; ++c)
+          if (lb[c] >= ub[c]) return why = "squashing bounds need lb < ub", -1;
+        // (a = (smooth (ub - lb))^2; at a = 0, ds/du is 0/0 on a bound)
+        for (int c = 0; c < nu; ++c)
+          if (!(a[c] > 0.)) return why = "squashing needs a positive smoothing term (smooth > 0)", -1;
+      }
       o += want;
     }
   }
@@ -307,7 +324,7 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
   if (njac > kMaxJacCosts) return why = "more than 8 frame / CoM / frame-velocity / free-flyer state costs in one knot", -1;
   const int nrows = count_cost_rows(parse(P), nu);
   if (nrows > kMaxCostRows) return why = "more than 64 cost residual rows with dense Jacobians in one knot", -1;
-  if ((pad2(diff_layout(nj, njac, nc, vcols, nu, nrows, 0, act).total) + pad2(size)) * 8 > 160 * 1024)
+  if ((pad2(diff_layout(nj, njac, nc, vcols, nu, nrows, 0, act, sat).total) + pad2(size)) * 8 > 160 * 1024)
     return why = "too many dofs for the calcDiff LDS plan", -1;
   if (nj_out) *nj_out = std::max(*nj_out, nj);
   if (njac_out) *njac_out = std::max(*njac_out, njac);
@@ -317,6 +334,7 @@ inline int64_t mb_block_check(const double* P, int64_t avail, int kind, int nx, 
   if (nrows_out) *nrows_out = std::max(*nrows_out, nrows);
   if (act_out) *act_out = *act_out || act;
   if (pris_out) *pris_out = *pris_out || pris;
+  if (sat_out) *sat_out = *sat_out || sat;
   return size;
 }
 
@@ -340,7 +358,7 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
   // one workgroup per CU, against the largest knot's 79.6 KB)
   struct MbShape {
     int nj, njac, nc, nu, nrows;
-    bool vcols, act;
+    bool vcols, act, sat;
   };
   std::vector<MbShape> shapes;
   const char* refused = nullptr;  // the first block refusal
@@ -354,10 +372,10 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
       for (int b = 0; b < nb; ++b) {
         const int64_t off = knots[t].param_offset + (int64_t)b * knots[t].param_stride;
         Refusal why;
-        MbShape k{0, 0, 0, 0, 0, false, false};
+        MbShape k{0, 0, 0, 0, 0, false, false, false};
         bool pris = false;
         const int64_t s1 = mb_block_check(params + off, n_params - off, knots[t].kind, d.nx, knots[t].nu, why, &k.nj,
-                                          &k.njac, &k.nc, &k.vcols, &k.nu, &k.nrows, &k.act, &pris);
+                                          &k.njac, &k.nc, &k.vcols, &k.nu, &k.nrows, &k.act, &pris, &k.sat);
         if (s1 < 0 && !refused) refused = why.text;
         if (s1 >= 0 && fddp::mb::has_impulse_com(fddp::mb::parse(params + off))) p.has_icom = true;
         if (s1 >= 0 && fddp::mb::has_momentum(fddp::mb::parse(params + off))) p.has_hmom = true;
@@ -378,7 +396,7 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
         bool seen = false;
         for (const MbShape& q : shapes)
           seen = seen || (q.nj == k.nj && q.njac == k.njac && q.nc == k.nc && q.nu == k.nu && q.nrows == k.nrows &&
-                          q.vcols == k.vcols && q.act == k.act);
+                          q.vcols == k.vcols && q.act == k.act && q.sat == k.sat);
         if (!seen) shapes.push_back(k);
       }
     } else {
@@ -402,7 +420,7 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
     int64_t mx = 0;
     for (const MbShape& q : shapes)
       mx = std::max<int64_t>(
-          mx, pad2(fddp::mb::diff_layout(q.nj, q.njac, q.nc, q.vcols, q.nu, q.nrows, spill, q.act).total));
+          mx, pad2(fddp::mb::diff_layout(q.nj, q.njac, q.nc, q.vcols, q.nu, q.nrows, spill, q.act, q.sat).total));
     return mx;
   };
   p.mb_all_lds = p.has_mb ? (plan_doubles(0) + pad2(mb_pmax)) * 8 : 0;

@@ -160,6 +160,7 @@ enum {
                               // [href(6)] (centroidal-momentum.hxx); Euler knots only
 };
 constexpr int C_ACTUATION = 20;  // the actuation record after the contact records: S (nv x nu, column-major)
+enum { SQ_NONE = 0, SQ_SMOOTH_SAT = 1 };  // its header slot 1: the squashing kind (smooth-sat.hpp)
 // Activation of a cost record: header slot 2 (core/activations/*.hpp)
 enum { A_QUAD = 0, A_WEIGHTED_QUAD = 1, A_QUAD_BARRIER = 2, A_WEIGHTED_QUAD_BARRIER = 3 };
 constexpr int kInactiveForceRow = -2;  // force cost on an inactive contact / impulse: lambda = 0, no Jacobians
@@ -182,6 +183,9 @@ struct Blk {
   int nun;            // leading unactuated dofs: tau = [0_nun; u], nu = nj - nun
                       // (with an actuation record: nj - nu, so that nu = nj - nun holds everywhere)
   const double* S;    // the actuation record's matrix dtau/du (nj x nu, column-major): tau = S u; null without
+#if MB_ACTUATION
+  const double* sq;   // squashing kind 1 (smooth-sat) of that record: lb(nu), ub(nu), a(nu), tau = S s(u); null without
+#endif
   int ncon, nc;       // active contact records, stacked rows
   double damping;     // JMinvJt_damping
   const double* K;    // contact records
@@ -205,7 +209,26 @@ inline double act_row_dot(const double* S, const double* u, int nj, int nu, int 
   for (int c = 0; c < nu; ++c) s += S[(int64_t)c * nj + i] * u[c];
   return s;
 }
+// Smooth-sat squashing of control c (record slots lb, ub, a at sq, nu apart; LDS on the device):
+//   s = 0.5 (sqrt((u - lb)^2 + a) - sqrt((u - ub)^2 + a) + lb + ub),
+//   D = ds/du = 0.5 ((u - lb) / sqrt((u - lb)^2 + a) - (u - ub) / sqrt((u - ub)^2 + a)),
+// two square roots per control (a > 0: the launch plan refuses a = 0, where D is 0/0 on a bound).
+// Out of line on the device, as act_row_dot. s into o[c]; with `diff` (the calcDiff) D into o[nu + c].
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __attribute__((noinline)) void squash_eval(const double* sq_, int nu, int c, double u, double* o_, bool diff) {
+  const double* sq = ::fddp::lds_ptr(sq_);
+  double* o = ::fddp::lds_ptr(o_);
+#else
+inline void squash_eval(const double* sq, int nu, int c, double u, double* o, bool diff) {
+#endif
+  const double lb = sq[c], ub = sq[nu + c], a = sq[2 * nu + c];
+  const double dl = u - lb, du = u - ub;
+  const double rl = sqrt(dl * dl + a), ru = sqrt(du * du + a);
+  o[c] = 0.5 * (rl - ru + lb + ub);
+  if (diff) o[nu + c] = 0.5 * (dl / rl - du / ru);
+}
 // tau_i of the knot's actuation at u (nu entries): S u with an actuation record, else [0_nun; u]
+// (a squashed record: the caller passes s(u), formed once per knot by squash_eval)
 MB_HD __forceinline__ double act_tau(const Blk& b, const double* u, int i) {
 #if MB_ACTUATION
   if (b.S) return act_row_dot(b.S, u, b.nj, b.nj - b.nun, i);
@@ -257,6 +280,9 @@ MB_HD inline Blk parse(const double* P) {
   b.enable_force = false;
   b.r_coeff = 0.;
   b.S = nullptr;
+#if MB_ACTUATION
+  b.sq = nullptr;
+#endif
   if (e - P < (int64_t)P[3]) {  // [nun | r_coeff, damping, ncontact, 0 | 1 | 2 | 3] + records
     b.impulse = ((int)e[3] & 1) != 0;
     b.enable_force = ((int)e[3] & 2) != 0;
@@ -272,8 +298,11 @@ MB_HD inline Blk parse(const double* P) {
     }
 #if MB_ACTUATION
     if (((int)e[3] & 4) != 0) {  // [20, 0, 0, 4 + nv nu] + S: tau = S u
-      b.nun = b.nj - ((int)r[3] - 4) / b.nj;
+      const bool sat = (int)r[1] == SQ_SMOOTH_SAT;  // [20, 1, 0, 4 + nv nu + 3 nu] + S + lb + ub + a: tau = S s(u)
+      const int nu = ((int)r[3] - 4) / (sat ? b.nj + 3 : b.nj);
+      b.nun = b.nj - nu;
       b.S = r + 4;
+      if (sat) b.sq = b.S + (int64_t)b.nj * nu;
     }
 #endif
   }
@@ -329,6 +358,9 @@ MB_HD __forceinline__ Blk parse_uniform(const double* P) {
   b.C = mb_uniform(b.C);
   b.nun = mb_uniform(b.nun);
   b.S = b.S ? mb_uniform(b.S) : nullptr;
+#if MB_ACTUATION
+  b.sq = b.sq ? mb_uniform(b.sq) : nullptr;
+#endif
   b.ncon = mb_uniform(b.ncon);
   b.nc = mb_uniform(b.nc);
   b.damping = mb_uniform(b.damping);

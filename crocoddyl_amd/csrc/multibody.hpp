@@ -748,6 +748,10 @@ MB_HD __forceinline__ double knot_calc_x(const X& ex, const double* P, int nx, c
   const WVals W{w, nj, pb + 128};            // the recursions' per-wave partials after it
   ex.run([&](int lane) {
     if (lane < nu) ub[lane] = use_u ? u[lane] : 0.;
+#if MB_ACTUATION
+    // (a squashed record: s(u) once per knot, into xnext, which is not written before the last phase)
+    if (b.sq && lane < nu) squash_eval(b.sq, nu, lane, use_u ? u[lane] : 0., xnext, false);
+#endif
     for (int e = lane; e < lda * ncol; e += ex.nt) A[e] = 0.;
   });
   // the wide records (state / control residuals: x, u only) row-parallel on waves 3 and 1
@@ -780,7 +784,11 @@ MB_HD __forceinline__ double knot_calc_x(const X& ex, const double* P, int nx, c
   if (!imp) world_rnea(ex, b, W, x + nq, nullptr, tau);
   ex.run([&](int lane) {
     if (lane < nj) {
-      const double ti = act_tau(b, ub, lane);  // tau = [0_nun; u], or S u with an actuation record
+#if MB_ACTUATION
+      const double ti = act_tau(b, b.sq ? xnext : ub, lane);  // tau = [0_nun; u], or S u / S s(u) with an actuation record
+#else
+      const double ti = act_tau(b, ub, lane);  // tau = [0_nun; u]
+#endif
       if (!imp) A[(int64_t)lda * (nj + nc) + lane] = ti - tau[lane];
       if (nc) contact_jac_lane(b, W, lane, Jc, A, lda);
     }
@@ -934,6 +942,10 @@ MB_HD __forceinline__ double knot_calc_dense_x(const X& ex, const double* P, int
   const int npw = part_waves(ex.nt);
   ex.run([&](int lane) {
     if (lane < nu) ub[lane] = use_u ? u[lane] : 0.;
+#if MB_ACTUATION
+    // (a squashed record: s(u) once per knot, into xnext, which is not written before the last phase)
+    if (b.sq && lane < nu) squash_eval(b.sq, nu, lane, use_u ? u[lane] : 0., xnext, false);
+#endif
   });
   // local placements; the wide records (state / control residuals: x, u only) row-parallel
   // on waves 3 and 1, their lane partials into pb
@@ -1003,7 +1015,11 @@ MB_HD __forceinline__ double knot_calc_dense_x(const X& ex, const double* P, int
   });
   ex.run([&](int lane) {
     if (lane < nj) {
-      const double ti = act_tau(b, ub, lane);  // tau = [0_nun; u], or S u with an actuation record
+#if MB_ACTUATION
+      const double ti = act_tau(b, b.sq ? xnext : ub, lane);  // tau = [0_nun; u], or S u / S s(u) with an actuation record
+#else
+      const double ti = act_tau(b, ub, lane);  // tau = [0_nun; u]
+#endif
       if (!imp) A[(int64_t)lda * (nj + nc) + lane] = ti - tau[lane];
       if (nc) contact_jac_lane(b, W, lane, Jc, A, lda);
     }
@@ -1145,6 +1161,8 @@ struct DiffLayout {
   // with an actuation record: Kinv_atau S (nj x nu at ld lda_of(nj)), da phase .. Fu; -1 without
   // (all-LDS plan: over the first half of A; spilled plan: an area of its own)
   int64_t KS, ksz;
+  // with a squashed record: s(u) and D(u) = ds/du (nu each), first phase .. Fu; -1 without (an area of its own)
+  int64_t sq, sqsz;
   int spill;       // kSpill* flags the plan was made with
   int64_t ht;      // host emulation: its factorisation scratch (70 nj)
   int64_t htotal;  // host emulation: total plus its own areas (da, the factorisation scratch)
@@ -1175,12 +1193,15 @@ MB_HD __forceinline__ int64_t cost_area_doubles(int nj, int nu, int nrows) {
   return cost_table_doubles() + kMaxCostCols + (int64_t)nrows * cost_rows_ld(nj, nu);
 }
 __host__ __device__ inline DiffLayout diff_layout(int nj, int njac, int nc = 0, bool vel_cols = false, int nu = 0,
-                                                  int nrows = 0, int spill = 0, bool act = false) {
+                                                  int nrows = 0, int spill = 0, bool act = false,
+                                                  bool sat = false) {
   const int L = 2 * nj;
   DiffLayout l;
   l.spill = spill;
   l.KS = -1;
   l.ksz = act ? (int64_t)lda_of(nj) * nu : 0;
+  l.sq = -1;
+  l.sqsz = act && sat ? 2 * (int64_t)nu : 0;
   const int64_t jsz = (int64_t)6 * (vel_cols ? L : nj) * (njac > 0 ? njac : 1);  // jac-cost Jacobians [cost][6][jw]
   const int64_t ca = cost_area_doubles(nj, nu, nrows);
   const int64_t wvs = pad2(WVals::doubles(nj));
@@ -1226,6 +1247,10 @@ __host__ __device__ inline DiffLayout diff_layout(int nj, int njac, int nc = 0, 
     l.Rr = l.R + cost_table_doubles();
     l.dts = l.dtau;
     if (act) l.KS = l.A;  // over M and its factors, dead since M^-1 (nu <= nj columns at the same ld)
+    if (l.sqsz) {
+      l.sq = pad2(l.total);
+      l.total = l.sq + l.sqsz;
+    }
     l.ht = pad2(l.total);  // host: the factorisation scratch
     l.htotal = l.ht + pad2((int64_t)70 * nj);
     return l;
@@ -1303,6 +1328,10 @@ __host__ __device__ inline DiffLayout diff_layout(int nj, int njac, int nc = 0, 
     l.KS = pad2(l.total);
     l.total = l.KS + l.ksz;
   }
+  if (l.sqsz) {
+    l.sq = pad2(l.total);
+    l.total = l.sq + l.sqsz;
+  }
   // host emulation: the da area and the factorisation's scratch of its own
   l.da = pad2(l.total);
   l.ht = l.da + pad2((int64_t)nj * (L + 1));
@@ -1314,8 +1343,8 @@ __host__ __device__ inline DiffLayout diff_layout(int nj, int njac, int nc = 0, 
 // and their sums (84 nj doubles) to fit in the Fx block (4 nj^2); the Jacobians go to
 // Lxu (2 nj m), d lambda / dx, du to Fu (2 nj m) when they fit.
 MB_HD inline int diff_spill(int nj, int njac, int nc, bool vcols, int nu, int nrows, int64_t psz, int m,
-                            bool act = false) {
-  const DiffLayout a = diff_layout(nj, njac, nc, vcols, nu, nrows, 0, act);
+                            bool act = false, bool sat = false) {
+  const DiffLayout a = diff_layout(nj, njac, nc, vcols, nu, nrows, 0, act, sat);
   if ((pad2(a.total) + pad2(psz)) * 8 <= 80 * 1024 || 84 * (int64_t)nj > 4 * (int64_t)nj * nj) return 0;
   const int64_t jsz = (int64_t)6 * (vcols ? 2 * nj : nj) * (njac > 0 ? njac : 1);
   const int64_t fsz = pad2((int64_t)nc * 2 * nj) + (int64_t)nc * nj;
@@ -1384,6 +1413,7 @@ MB_HD inline int diff_layout_regions(const DiffLayout& l, int nj, int njac, int 
   add("cost diagonal / rows", l.Rr, cost_area_doubles(nj, nu, nrows) - cost_table_doubles(), DP_RROWS, DP_END);
   if (sp && l.dts >= 0) add("dtau (LDS copy)", l.dts, (int64_t)nj * L, DP_DA, DP_DA);
   add("Kinv S (actuation record)", l.KS, l.ksz, DP_DA, DP_END);
+  add("s(u), ds/du (squashed record)", l.sq, l.sqsz, DP_INIT, DP_END);
   return k;
 }
 // 0 when no two regions of the plan overlap in both LDS and live range (and all lie in
@@ -2327,32 +2357,38 @@ MB_HD inline void impulse_com_rows(int lane, int nt, const double* csrc, const d
 // The two products of an actuation record (tau = S u, S nj x nu column-major) in the calcDiff, on
 // every lane of the workgroup: d lambda / du (k, c) = -sum_i H(k, i) S(i, c) into dfu (nc x nj,
 // its columns beyond nu zero; null: no force Jacobians) and Kinv_atau S into KS (nj x nu at ld
-// lda). Out of line on the device, as act_row_dot. dfu may be the knot's Fu block (kSpillF).
+// lda). A squashed record (tau = S s(u), Dq = ds/du, nu entries; null without): column c of both
+// is scaled by Dq[c] here, where they are written, so that their readers (the Fu assembly, the
+// force costs' rows) are the linear record's. Out of line on the device, as act_row_dot. dfu may
+// be the knot's Fu block (kSpillF).
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __attribute__((noinline)) void act_products(int lane, int nt, const double* S_, const double* Kinv_, int lda,
                                                        const double* H_, int nj, int nu, int nc, double* dfu,
-                                                       double* KS_) {
+                                                       double* KS_, const double* Dq_) {
   const double* S = lds_ptr(S_);
   const double* Kinv = lds_ptr(Kinv_);
   const double* H = lds_ptr(H_);
   double* KS = lds_ptr(KS_);
+  const double* Dq = Dq_ ? lds_ptr(Dq_) : nullptr;
 #else
 inline void act_products(int lane, int nt, const double* S, const double* Kinv, int lda, const double* H, int nj, int nu,
-                         int nc, double* dfu, double* KS) {
+                         int nc, double* dfu, double* KS, const double* Dq) {
 #endif
   if (dfu)
     for (int e = lane; e < nc * nj; e += nt) {
       const int k = e / nj, c = e % nj;
       double s = 0.;
-      if (c < nu)
+      if (c < nu) {
         for (int i = 0; i < nj; ++i) s -= H[(int64_t)k * nj + i] * S[(int64_t)c * nj + i];
+        if (Dq) s *= Dq[c];
+      }
       dfu[e] = s;
     }
   for (int e = lane; e < nj * nu; e += nt) {
     const int c = e / nj, i = e % nj;
     double s = 0.;
     for (int k = 0; k < nj; ++k) s += Kinv[(int64_t)k * lda + i] * S[(int64_t)c * nj + k];
-    KS[(int64_t)c * lda + i] = s;
+    KS[(int64_t)c * lda + i] = Dq ? s * Dq[c] : s;
   }
 }
 
@@ -2376,7 +2412,13 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
   // (calc only, Fx == nullptr: the same plan; it ends before any spilled array is used)
   if (SP == 0) spill = 0;
   if (SP == 1) spill |= kSpillBlocks;
+#if MB_ACTUATION
+  const DiffLayout l = diff_layout(nj, njac, nc, vcols, nu, nrows, spill, b.S != nullptr, b.sq != nullptr);
+  // (a squashed record: s(u), then D(u) = ds/du, one entry per control, formed in the first phase)
+  double* const sqs = (b.sq && !imp) ? w + l.sq : nullptr;
+#else
   const DiffLayout l = diff_layout(nj, njac, nc, vcols, nu, nrows, spill, b.S != nullptr);
+#endif
   const bool spilled = SP >= 0 ? SP == 1 : (spill & kSpillBlocks) != 0;
   // the recursions' per-wave partials (free areas of their phases: DiffLayout)
   const WVals W{w + l.wv, nj, w + l.pk};
@@ -2493,15 +2535,20 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
   Minv = ex.lds(Minv);
   MB_DUMP(4, Minv, nj, nj, lda);
 #if MB_ACTUATION
-  // (an actuation record: tau = S u once per dof, -(tau - nle) over nle, which is dead after
+  // (an actuation record: tau = S u, or S s(u), once per dof, -(tau - nle) over nle, which is dead after
   // the next phase; the branch is uniform)
   const double* const Sa = (b.S && !imp) ? ex.lds(b.S) : nullptr;
+  if (sqs)  // (s(u) and ds/du, two square roots per control, once per knot)
+    ex.run([&](int lane) {
+      if (lane < nu) squash_eval(b.sq, nu, lane, u[lane], sqs, true);
+    });
   if (Sa)
     ex.run([&](int lane) {
-      if (lane < nj) nle[lane] = -(act_tau(b, u, lane) - nle[lane]);
+      if (lane < nj) nle[lane] = -(act_tau(b, sqs ? sqs : u, lane) - nle[lane]);
     });
 #else
   const double* const Sa = nullptr;
+  const double* const sqs = nullptr;
 #endif
   // z = (M + A)^-1 (tau - nle) (the acceleration without contacts); Y = Minv Jc^T
   ex.run([&](int lane) {
@@ -2818,8 +2865,8 @@ MB_HD __forceinline__ void knot_calc_diff_x(const X& ex, const double* P, int nx
         }
     }
     // an actuation record: d lambda / du = -H^T S and da / du = Kinv_atau S (what the Fu assembly
-    // reads), each formed once per knot
-    if (Sa) act_products(lane, ex.nt, Sa, ex.lds(Minv), lda, ex.lds(H), nj, nu, nc, fd ? dfu : nullptr, ex.lds(w + l.KS));
+    // reads), each formed once per knot (squashed: their columns times ds/du)
+    if (Sa) act_products(lane, ex.nt, Sa, ex.lds(Minv), lda, ex.lds(H), nj, nu, nc, fd ? dfu : nullptr, ex.lds(w + l.KS), sqs ? sqs + nu : nullptr);
     // the cost-derivative table: groups in cost (name) order, each the rows of one cost
     // with a dense residual Jacobian, or the diagonal of a state / control cost; per row
     // Arr (hess), and Ar as amul * aval (the quadratic kinds' (w, r), so the gradient

@@ -10,6 +10,8 @@ Reference API mirrored:
   ActuationModelFloatingBase(state)             multibody/actuations/floating-base.hpp
   ActuationModelMultiCopterBase(state, n, tau_f) multibody/actuations/multicopter-base.hpp
   ActuationModelLinear(state, S)                tau = S u, S constant (a project extension)
+  ActuationSquashingModel(actuation, squashing, nu), SquashingModelSmoothSat(u_lb, u_ub, ns)
+                                                core/actuation/actuation-squashing.hpp, squashing/smooth-sat.hpp
   ActivationModelQuad(nr), ActivationModelWeightedQuad(weights)
                                                 core/activations/{quadratic,weighted-quadratic}.hpp
   CostModelSum(state, nu).addCost(name, cost, weight)   multibody/costs/cost-sum.hxx:18-85
@@ -672,6 +674,10 @@ class ActuationModelLinear:
         """S of batch element b (the one matrix when there is no batch axis)."""
         return self._S[b].copy() if self._S.ndim == 3 else self._S.copy()
 
+    def dtau_du0(self, b=0):
+        """dtau/du at u = 0 (what quasiStatic inverts): S itself."""
+        return self.matrix(b)
+
     def pack(self):
         """(Bm, 4 + nv nu) rows of the actuation record: [20, 0, 0, size] + S column-major."""
         S = self._S if self._S.ndim == 3 else self._S[None]
@@ -705,6 +711,135 @@ class ActuationModelMultiCopterBase(ActuationModelLinear):
         S[..., :6, :n_rotors] = tau_f
         S[..., 6:, n_rotors:] = np.eye(nv - 6)
         super().__init__(state, S)
+
+
+SQUASH_NONE, SQUASH_SMOOTH_SAT = 0, 1  # header slot 1 of the actuation record (include/fddp_hip.h)
+
+
+class SquashingModelSmoothSat:
+    """SquashingModelSmoothSat(u_lb, u_ub, ns) (core/actuation/squashing/smooth-sat.hpp): per control
+        s = 0.5 (sqrt((u - lb)^2 + a) - sqrt((u - ub)^2 + a) + lb + ub),  a = (smooth (ub - lb))^2,
+    a smooth saturation of u into (lb, ub) with ds/du in (0, 1). ``smooth`` defaults to 0.1. The bounds
+    may carry a leading batch axis (B, ns): one pair per problem of the batch. Assigning the bounds or
+    ``smooth`` anew re-uploads on a live handle."""
+
+    def __init__(self, u_lb, u_ub, ns):
+        self.ns = int(ns)
+        self._version = 0
+        self._smooth = 0.1
+        self._set_bounds(u_lb, u_ub)
+
+    def _set_bounds(self, lb, ub):
+        lb, ub = np.array(lb, np.float64), np.array(ub, np.float64)
+        for v in (lb, ub):
+            if v.ndim not in (1, 2) or v.shape[-1] != self.ns:
+                raise ValueError(f"Invalid argument: u_lb / u_ub has wrong dimension (it should be {self.ns})")
+        if lb.ndim == 2 and ub.ndim == 2 and lb.shape[0] != ub.shape[0]:
+            raise ValueError("Invalid argument: u_lb and u_ub carry different batch sizes")
+        if not (np.isfinite(lb).all() and np.isfinite(ub).all()):
+            raise ValueError("Invalid argument: the squashing bounds have a non-finite entry")
+        if not (lb < ub).all():
+            raise ValueError("Invalid argument: the squashing bounds need u_lb < u_ub")
+        self._lb, self._ub = lb, ub
+        self._a = (self._smooth * (ub - lb)) ** 2
+        self._version += 1
+
+    s_lb = property(lambda self: self._lb.copy(), lambda self, v: self._set_bounds(v, self._ub))
+    s_ub = property(lambda self: self._ub.copy(), lambda self, v: self._set_bounds(self._lb, v))
+    u_lb, u_ub = s_lb, s_ub
+
+    @property
+    def smooth(self):
+        return self._smooth
+
+    @smooth.setter
+    def smooth(self, smooth):
+        if smooth < 0.0:
+            raise ValueError("Invalid argument: The smooth value has to be positive")
+        self._smooth = float(smooth)
+        self._set_bounds(self._lb, self._ub)
+
+    def _rows(self, b):
+        a = np.broadcast_to(self._a, np.broadcast_shapes(self._lb.shape, self._ub.shape))
+        pick = lambda v: v[b] if v.ndim == 2 else v
+        return pick(self._lb), pick(self._ub), pick(a)
+
+    def calc(self, u, b=0):
+        """s(u) (batch element b's bounds)."""
+        lb, ub, a = self._rows(b)
+        u = np.asarray(u, np.float64)
+        return 0.5 * (np.sqrt((u - lb) ** 2 + a) - np.sqrt((u - ub) ** 2 + a) + lb + ub)
+
+    def calcDiff(self, u, b=0):
+        """ds/du at u: the ns x ns diagonal matrix."""
+        lb, ub, a = self._rows(b)
+        u = np.asarray(u, np.float64)
+        return np.diag(0.5 * ((u - lb) / np.sqrt((u - lb) ** 2 + a) - (u - ub) / np.sqrt((u - ub) ** 2 + a)))
+
+    def pack(self):
+        """(Bm, 3 ns) rows [lb, ub, a] of the actuation record's squashing part."""
+        shape = np.broadcast_shapes(self._lb.shape, self._ub.shape)
+        rows = [np.broadcast_to(v, shape).reshape(-1, self.ns) for v in (self._lb, self._ub, self._a)]
+        return np.concatenate(rows, axis=1)
+
+
+class ActuationSquashingModel(ActuationModelLinear):
+    """ActuationSquashingModel(actuation, squashing, nu) (core/actuation/actuation-squashing.hpp):
+    tau = actuation(s(u)), here tau = S s(u) with dtau/du = S diag(ds/du) and dtau/dx = 0. The inner
+    actuation is an ActuationModelLinear / ActuationModelMultiCopterBase (its S), or an
+    ActuationModelFull / ActuationModelFloatingBase (S written as the selection matrix). Costs and
+    control limits still act on u. It takes the place of a linear actuation in both differential
+    models (the actuation record with squashing kind 1)."""
+
+    def __init__(self, actuation, squashing, nu):
+        if not isinstance(actuation, (ActuationModelLinear, ActuationModelFull, ActuationModelFloatingBase)) or \
+                isinstance(actuation, ActuationSquashingModel):
+            raise NotImplementedError("crocoddyl_amd: ActuationSquashingModel wraps an ActuationModelFull, "
+                                      "ActuationModelFloatingBase, ActuationModelMultiCopterBase or "
+                                      "ActuationModelLinear")
+        if not isinstance(squashing, SquashingModelSmoothSat):
+            raise NotImplementedError("crocoddyl_amd: the device path covers SquashingModelSmoothSat only")
+        nu = int(nu)
+        if nu != actuation.nu:
+            raise ValueError(f"Invalid argument: nu has wrong dimension (it should be {actuation.nu})")
+        if squashing.ns != nu:
+            raise ValueError(f"Invalid argument: ns has wrong dimension (it should be {nu})")
+        self.state = actuation.state
+        self.nu = nu
+        self._actuation, self._squashing = actuation, squashing
+
+    actuation = property(lambda self: self._actuation)
+    squashing = property(lambda self: self._squashing)
+
+    @property
+    def _S(self):
+        if isinstance(self._actuation, ActuationModelLinear):
+            return self._actuation._S
+        nv = self.state.nv
+        return np.vstack([np.zeros((nv - self.nu, self.nu)), np.eye(self.nu)])
+
+    @property
+    def S(self):
+        return self._S.copy()
+
+    @property
+    def _version(self):
+        return (getattr(self._actuation, "_version", 0), self._squashing._version)
+
+    def dtau_du0(self, b=0):
+        """dtau/du at u = 0: S diag(ds/du(0)) (quasiStatic linearises the squashing there)."""
+        return self.matrix(b) @ self._squashing.calcDiff(np.zeros(self.nu), b)
+
+    def pack(self):
+        """(Bm, 4 + nv nu + 3 nu) rows: [20, 1, 0, size] + S column-major + lb + ub + a."""
+        S = self._S if self._S.ndim == 3 else self._S[None]
+        flat = S.transpose(0, 2, 1).reshape(S.shape[0], -1)
+        sq = self._squashing.pack()
+        if flat.shape[0] != sq.shape[0] and 1 not in (flat.shape[0], sq.shape[0]):
+            raise ValueError("Invalid argument: S and the squashing bounds carry different batch sizes")
+        Bm = max(flat.shape[0], sq.shape[0])
+        hdr = np.array([[ACTUATION_REC, float(SQUASH_SMOOTH_SAT), 0.0, 4 + flat.shape[1] + sq.shape[1]]])
+        return np.concatenate([np.broadcast_to(p, (Bm, p.shape[1])) for p in (hdr, flat, sq)], axis=1)
 
 
 ACT_QUAD, ACT_WEIGHTED_QUAD, ACT_QUAD_BARRIER, ACT_WEIGHTED_QUAD_BARRIER = 0, 1, 2, 3
@@ -1507,7 +1642,7 @@ class DifferentialActionModelFreeFwdDynamics(_ControlLimits):
         x = np.asarray(x, float)
         g = self.state.pinocchio.computeGeneralizedGravity(x[:self.state.nq])
         if isinstance(self.actuation, ActuationModelLinear):
-            return np.linalg.pinv(self.actuation.matrix()) @ g
+            return np.linalg.pinv(self.actuation.dtau_du0()) @ g
         return g[self.state.nv - self.nu:].copy()
 
     def pack_body(self, dt):
@@ -1718,7 +1853,7 @@ class DifferentialActionModelContactFwdDynamics(DifferentialActionModelFreeFwdDy
         model, nv, nu = self.state.pinocchio, self.state.nv, self.nu
         q = x[:self.state.nq]
         g = model.computeGeneralizedGravity(q)
-        cols = [self.actuation.matrix() if isinstance(self.actuation, ActuationModelLinear)
+        cols = [self.actuation.dtau_du0() if isinstance(self.actuation, ActuationModelLinear)
                 else np.vstack([np.zeros((nv - nu, nu)), np.eye(nu)])]
         for n in self.contacts.active:
             c = self.contacts.contacts[n].contact

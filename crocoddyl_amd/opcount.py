@@ -184,6 +184,11 @@ def knot_flops(model):
         # da/du = Kinv_atau S, and with enable_force d lambda / du = -H^T S
         calc += 2 * n * nu
         diff += 2 * n * nu + 2 * n * n * nu + (2 * nc * n * nu if nc and dam.enable_force else 0)
+        if isinstance(dam.actuation, mb.ActuationSquashingModel):
+            # s(u): two square roots per control and 8 flops around them (both calcs); ds/du: two
+            # divisions and 2 flops more; column c of both products times ds/du_c
+            calc += 10 * nu
+            diff += 10 * nu + 4 * nu + n * nu + (nc * nu if nc and dam.enable_force else 0)
     return float(calc), float(diff)
 
 

@@ -13,7 +13,8 @@ reference configurations), as ``crocoddyl_amd.multibody.RobotModel`` objects.
                    arms 2 x 7 + grippers 2, head 2): nq = 39, nv = 38 (C5)
   sample_solo12(): free-flyer + 4 legs x 3 (HAA, HFE, KFE): nq = 19, nv = 18 (C4)
   sample_quadrotor(arm_joints=0): a free-flyer base body, optionally with a short revolute
-                   chain below it (nv = 6 + arm_joints); quadrotor_tau_f(): the rotor map
+                   chain below it (nv = 6 + arm_joints); quadrotor_tau_f(): the rotor map;
+                   sample_quadrotor_ubound(): the same with thrust limits as a smooth saturation
   sample_cartpole(): a prismatic cart along x carrying a revolute pole about y (nv = 2)
   sample_hopper(legs=2): a free-flyer body on telescopic legs, a revolute hip and a prismatic
                    shank each (nv = 6 + 2 legs)
@@ -154,6 +155,23 @@ def quadrotor_tau_f(d=0.1525, cf=6.6e-5, cm=1e-6):
     r = cm / cf
     return np.array([[0.0, 0.0, 0.0, 0.0], [0.0, 0.0, 0.0, 0.0], [1.0, 1.0, 1.0, 1.0], [0.0, d, 0.0, -d],
                      [-d, 0.0, d, 0.0], [-r, r, -r, r]])
+
+
+def sample_quadrotor_ubound(arm_joints=0, thrust_lb=0.1, thrust_ub=10.3, arm_torque=2.0, smooth=0.1):
+    """The quadrotor of the reference's quadrotor_ubound example: sample_quadrotor(arm_joints) with
+    its rotor actuation wrapped in a smooth saturation, tau = S s(u), the thrusts held in
+    (thrust_lb, thrust_ub) and the arm torques in (-arm_torque, arm_torque) by the dynamics
+    (plain FDDP needs no control bounds then). Returns (model, state, actuation)."""
+    from .multibody import (ActuationModelMultiCopterBase, ActuationSquashingModel, SquashingModelSmoothSat,
+                            StateMultibody)
+    model = sample_quadrotor(arm_joints)
+    state = StateMultibody(model)
+    rotors = ActuationModelMultiCopterBase(state, 4, quadrotor_tau_f())
+    lb = np.concatenate([np.full(4, float(thrust_lb)), np.full(arm_joints, -float(arm_torque))])
+    ub = np.concatenate([np.full(4, float(thrust_ub)), np.full(arm_joints, float(arm_torque))])
+    squashing = SquashingModelSmoothSat(lb, ub, rotors.nu)
+    squashing.smooth = smooth
+    return model, state, ActuationSquashingModel(rotors, squashing, rotors.nu)
 
 
 def sample_cartpole(cart_mass=1.0, pole_mass=0.3, pole_length=0.8):

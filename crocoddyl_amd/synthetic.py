@@ -460,7 +460,10 @@ def build_arm(T=None, B=None, seed=None, robot=None, dt=1e-3, weighted=False, ar
 
 def _linear_actuation(mb, state, actuation):
     """The builders' ``actuation=`` option: "multicopter" (four rotors on the free-flyer base, the
-    quadrotor example's map) or a matrix S (nv x nu, optionally with a leading batch axis)."""
+    quadrotor example's map), a matrix S (nv x nu, optionally with a leading batch axis), or a
+    callable state -> actuation model (an ActuationSquashingModel around any of the others)."""
+    if callable(actuation):
+        return actuation(state)
     if isinstance(actuation, str):
         if actuation != "multicopter":
             raise ValueError(f"unknown actuation {actuation!r}")

@@ -15,6 +15,7 @@
 //   ActuationModelFull / ActuationModelFloatingBase   multibody/actuations/{full,floating-base}.hpp
 //   ActuationModelMultiCopterBase                     multibody/actuations/multicopter-base.hpp
 //   ActuationModelLinear (tau = S u, S constant)      a project extension
+//   ActuationSquashingModel, SquashingModelSmoothSat  core/actuation/actuation-squashing.hpp, squashing/smooth-sat.hpp
 //   ActivationModelQuad / WeightedQuad / QuadraticBarrier / WeightedQuadraticBarrier,
 //     ActivationBounds                        core/activations/*.hpp
 //   FrictionCone                              multibody/friction-cone.hxx:24-96
@@ -456,6 +457,9 @@ struct ActuationModelAbstract {
   // dtau/du of a linear actuation (nv x nu, column-major: the block's actuation record), or
   // null: tau = [0_nun; u]
   virtual const VectorXd* matrix() const { return nullptr; }
+  // the squashing part of the actuation record (lb, ub, a: nu entries each; squashing kind 1),
+  // or null: none
+  virtual const VectorXd* squashing() const { return nullptr; }
 };
 struct ActuationModelFull : ActuationModelAbstract {  // tau = u
   explicit ActuationModelFull(std::shared_ptr<StateMultibody> state) {
@@ -514,6 +518,93 @@ struct ActuationModelMultiCopterBase : ActuationModelLinear {
     for (int i = 6; i < nv; ++i) S[(size_t)(n_rotors + i - 6) * nv + i] = 1.;
     set(nv, S, m);
   }
+};
+
+// core/actuation/squashing/smooth-sat.hpp: per control
+//   s = 0.5 (sqrt((u - lb)^2 + a) - sqrt((u - ub)^2 + a) + lb + ub),  a = (smooth (ub - lb))^2,
+// a smooth saturation of u into (lb, ub) with ds/du in (0, 1); smooth defaults to 0.1.
+class SquashingModelSmoothSat {
+ public:
+  SquashingModelSmoothSat(const VectorXd& u_lb, const VectorXd& u_ub, int ns) : ns_(ns), smooth_(0.1) {
+    set_bounds(u_lb, u_ub);
+  }
+  int get_ns() const { return ns_; }
+  const VectorXd& get_s_lb() const { return lb_; }
+  const VectorXd& get_s_ub() const { return ub_; }
+  void set_s_lb(const VectorXd& lb) { set_bounds(lb, ub_); }
+  void set_s_ub(const VectorXd& ub) { set_bounds(lb_, ub); }
+  double get_smooth() const { return smooth_; }
+  void set_smooth(double smooth) {
+    if (smooth < 0.) throw Exception("Invalid argument: The smooth value has to be positive");
+    smooth_ = smooth;
+    set_bounds(lb_, ub_);
+  }
+  void calc(const VectorXd& u, VectorXd& s) const {
+    s.resize(ns_);
+    for (int c = 0; c < ns_; ++c)
+      s[c] = 0.5 * (std::sqrt((u[c] - lb_[c]) * (u[c] - lb_[c]) + a_[c]) -
+                    std::sqrt((u[c] - ub_[c]) * (u[c] - ub_[c]) + a_[c]) + lb_[c] + ub_[c]);
+  }
+  // the diagonal of ds/du
+  void calcDiff(const VectorXd& u, VectorXd& ds_du) const {
+    ds_du.resize(ns_);
+    for (int c = 0; c < ns_; ++c)
+      ds_du[c] = 0.5 * ((u[c] - lb_[c]) / std::sqrt((u[c] - lb_[c]) * (u[c] - lb_[c]) + a_[c]) -
+                        (u[c] - ub_[c]) / std::sqrt((u[c] - ub_[c]) * (u[c] - ub_[c]) + a_[c]));
+  }
+  // lb, ub, a: the record's squashing part
+  const VectorXd& packed() const { return packed_; }
+
+ private:
+  void set_bounds(const VectorXd& lb, const VectorXd& ub) {
+    if ((int)lb.size() != ns_ || (int)ub.size() != ns_)
+      throw Exception("Invalid argument: u_lb / u_ub has wrong dimension (it should be " + std::to_string(ns_) + ")");
+    for (int c = 0; c < ns_; ++c) {
+      if (!std::isfinite(lb[c]) || !std::isfinite(ub[c]))
+        throw Exception("Invalid argument: the squashing bounds have a non-finite entry");
+      if (!(lb[c] < ub[c])) throw Exception("Invalid argument: the squashing bounds need u_lb < u_ub");
+    }
+    lb_ = lb;
+    ub_ = ub;
+    a_.assign(ns_, 0.);
+    for (int c = 0; c < ns_; ++c) a_[c] = (smooth_ * (ub[c] - lb[c])) * (smooth_ * (ub[c] - lb[c]));
+    packed_ = lb_;
+    packed_.insert(packed_.end(), ub_.begin(), ub_.end());
+    packed_.insert(packed_.end(), a_.begin(), a_.end());
+  }
+  int ns_;
+  double smooth_;
+  VectorXd lb_, ub_, a_, packed_;
+};
+// core/actuation/actuation-squashing.hpp: tau = actuation(s(u)), here tau = S s(u) with
+// dtau/du = S diag(ds/du). The inner actuation is a linear one (its S), or the full / floating-base
+// one (S written as the selection matrix). Costs and control limits still act on u.
+struct ActuationSquashingModel : ActuationModelAbstract {
+  ActuationSquashingModel(std::shared_ptr<StateMultibody> state, std::shared_ptr<ActuationModelAbstract> actuation,
+                          std::shared_ptr<SquashingModelSmoothSat> squashing, int nu_)
+      : actuation_(actuation), squashing_(squashing) {
+    if (actuation->squashing()) throw Exception("Invalid argument: ActuationSquashingModel wraps an unsquashed actuation");
+    if (nu_ != actuation->nu)
+      throw Exception("Invalid argument: nu has wrong dimension (it should be " + std::to_string(actuation->nu) + ")");
+    if (squashing->get_ns() != nu_)
+      throw Exception("Invalid argument: ns has wrong dimension (it should be " + std::to_string(nu_) + ")");
+    nu = nu_;
+    if (!actuation->matrix()) {  // tau = [0; u]: the selection matrix
+      const int nv = state->get_nv();
+      S_.assign((size_t)nv * nu, 0.);
+      for (int c = 0; c < nu; ++c) S_[(size_t)c * nv + (nv - nu + c)] = 1.;
+    }
+  }
+  bool floating_base() const { return false; }
+  const VectorXd* matrix() const { return actuation_->matrix() ? actuation_->matrix() : &S_; }
+  const VectorXd* squashing() const { return &squashing_->packed(); }
+  const std::shared_ptr<ActuationModelAbstract>& get_actuation() const { return actuation_; }
+  const std::shared_ptr<SquashingModelSmoothSat>& get_squashing() const { return squashing_; }
+
+ private:
+  std::shared_ptr<ActuationModelAbstract> actuation_;
+  std::shared_ptr<SquashingModelSmoothSat> squashing_;
+  VectorXd S_;
 };
 
 // ---- activations (core/activations/*.hpp) ----------------------------------
@@ -1233,11 +1324,14 @@ class DifferentialActionModelFreeFwdDynamics : public DifferentialActionModelBas
     out[o + 3] = (double)(out.size() - o);
     return o;
   }
-  // the actuation record [20, 0, 0, 4 + nv nu] + S (column-major), after the contact records
+  // the actuation record [20, 0, 0, 4 + nv nu] + S (column-major), after the contact records;
+  // squashed: [20, 1, 0, 4 + nv nu + 3 nu] + S + lb + ub + a
   void pack_actuation(VectorXd& sec) const {
     const VectorXd& S = *actuation_->matrix();
-    sec.insert(sec.end(), {20., 0., 0., (double)(4 + S.size())});
+    const VectorXd* sq = actuation_->squashing();
+    sec.insert(sec.end(), {20., sq ? 1. : 0., 0., (double)(4 + S.size() + (sq ? sq->size() : 0))});
     sec.insert(sec.end(), S.begin(), S.end());
+    if (sq) sec.insert(sec.end(), sq->begin(), sq->end());
   }
   std::shared_ptr<StateMultibody> state_;
   std::shared_ptr<ActuationModelAbstract> actuation_;

@@ -153,7 +153,14 @@ int fddp_abi_version(void);
  * ncontact contact records comes one actuation record
  *   [type 20, 0, 0, size = 4 + nv nu], S (nv x nu, column-major), 1 <= nu <= nv,
  * with which the block ends. ncontact = 0 stays allowed (free dynamics under such an
- * actuation, as under the floating base). A block without bit 4 is read as before. */
+ * actuation, as under the floating base). A block without bit 4 is read as before.
+ * Header slot 1 of the actuation record is the squashing kind: 0 none (above), 1 the
+ * smooth saturation of ActuationSquashingModel with SquashingModelSmoothSat
+ * (core/actuation/actuation-squashing.hpp, squashing/smooth-sat.hpp): tau = S s(u),
+ *   s_c = 0.5 (sqrt((u_c - lb_c)^2 + a_c) - sqrt((u_c - ub_c)^2 + a_c) + lb_c + ub_c),
+ * dtau/du = S diag(ds/du), a_c = (smooth (ub_c - lb_c))^2. The record is then
+ *   [type 20, 1, 0, size = 4 + nv nu + 3 nu], S, lb (nu), ub (nu), a (nu),
+ * with finite entries, lb_c < ub_c and a_c > 0. Costs and control bounds act on u. */
 #define FDDP_KNOT_EULER_CONTACTFWD 5
 /* ActionModelImpulseFwdDynamics (multibody/actions/impulse-fwddyn.hxx:53-127): an
  * action model (no integrator), nu = 0, xnext = (q, v+) with the impulse
