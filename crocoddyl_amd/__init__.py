@@ -16,7 +16,7 @@ from .models import (ActionData, ActionDataAbstract, ActionModelAbstract, Action
                      DifferentialActionData, DifferentialActionDataAbstract, DifferentialActionModelAbstract,
                      DifferentialActionModelLQR, DifferentialActionModelNumDiff, IntegratedActionModelEuler,
                      StateVector)
-from .problem import ShootingProblem, SolverBoxFDDP, SolverFDDP, pack_problem  # noqa: F401
+from .problem import ShootingProblem, SolverBoxDDP, SolverBoxFDDP, SolverDDP, SolverFDDP, pack_problem  # noqa: F401
 from .boxqp import BoxQP, BoxQPSolution  # noqa: F401
 from .callbacks import CallbackAbstract, CallbackLogger, CallbackVerbose, VerboseLevel  # noqa: F401
 

@@ -25,7 +25,7 @@ Q_COST = 19
 Q_VXX, Q_VX, Q_QXX, Q_QXU, Q_QUU, Q_QX, Q_QU = range(11, 18)
 Q_QUU_INV = 18
 
-SOLVER_FDDP, SOLVER_BOXFDDP = 0, 1
+SOLVER_FDDP, SOLVER_BOXFDDP, SOLVER_DDP, SOLVER_BOXDDP = 0, 1, 2, 3
 
 # fddp_get_kernel_info: the kernel variants (csrc/ktab.hpp)
 MB_W2, MB_W1, MB_X2, MB_X8, MB_S2 = range(5)

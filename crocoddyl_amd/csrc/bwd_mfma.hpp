@@ -687,7 +687,7 @@ __device__ __forceinline__ bool box_gains_wave(const Dev& D, const BwdLds& L, in
 // One knot of the sweep, as executed by wave W (all four waves call this
 // with their own W; the barriers inside line up one to one).
 template <int NTL, int MTL, int NW, int W>
-__device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, int t, bool feas, double xreg,
+__device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, int t, bool feas, bool boxqp, double xreg,
                                          double ureg, int cur, Stamp& stamp, double (&red5)[5]) {
   using Cfg = MfmaCfg<NTL, MTL>;
   constexpr int NP = Cfg::NP, MP = Cfg::MP, JT = Cfg::JT, LDV = Cfg::LDV, LDQ = Cfg::LDQ, LDC = Cfg::LDC, ZLD = Cfg::ZLD;
@@ -711,7 +711,9 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
   const int q = lane >> 4, c = lane & 15;
   const bool xr = !isnan(xreg), ur = !isnan(ureg);
   const int64_t kk = D.knot(b, t), rr = D.run(b, t);
-  const bool boxk = feas && mu > 0 && D.box_knot(b, t);  // SolverBoxFDDP gains on this knot (box-fddp.cpp:47)
+  // SolverBoxFDDP gains on this knot (box-fddp.cpp:47); boxqp: the element's sweeps take the box QP
+  // (feasible, or SolverBoxDDP, whose QP runs while infeasible too: FDDP_BACKWARD_MFMA_BODY)
+  const bool boxk = boxqp && mu > 0 && D.box_knot(b, t);
   if constexpr (W != 0 && P.owns_u(W)) __builtin_amdgcn_s_setprio(2);  // Quu first: the inversion waits on it
   // the next knot's operands (LDS-DMA; lands during P2 / P3)
   // this knot's operand buffers (prefetch plan: by the knot's parity) and knot t-1's
@@ -1261,8 +1263,8 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
 }
 
 template <int NTL, int MTL, int NW>
-__device__ __forceinline__ bool bwd_sweep_mfma(const Dev& D, int b, bool feas, double xreg, double ureg, int cur,
-                                               double* sm, double (&ei)[3]) {
+__device__ __forceinline__ bool bwd_sweep_mfma(const Dev& D, int b, bool feas, bool boxqp, double xreg, double ureg,
+                                               int cur, double* sm, double (&ei)[3], bool ddp) {
   double red5[5] = {0., 0., 0., 0., 0.};  // running sums (C^T in its own area: the small shapes)
   using Cfg = MfmaCfg<NTL, MTL>;
   constexpr int NP = Cfg::NP, MP = Cfg::MP, LDV = Cfg::LDV, LDQ = Cfg::LDQ;
@@ -1387,14 +1389,14 @@ __device__ __forceinline__ bool bwd_sweep_mfma(const Dev& D, int b, bool feas, d
     stamp.mark(7);
     bool ok = false;
     switch (wid) {
-      case 0: ok = bwd_knot<NTL, MTL, NW, 0>(D, L, b, t, feas, xreg, ureg, cur, stamp, red5); break;
-      case 1: ok = bwd_knot<NTL, MTL, NW, 1>(D, L, b, t, feas, xreg, ureg, cur, stamp, red5); break;
-      case 2: ok = bwd_knot<NTL, MTL, NW, 2>(D, L, b, t, feas, xreg, ureg, cur, stamp, red5); break;
-      case 3: ok = bwd_knot<NTL, MTL, NW, 3>(D, L, b, t, feas, xreg, ureg, cur, stamp, red5); break;
-      case 4: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 4>(D, L, b, t, feas, xreg, ureg, cur, stamp, red5); break;
-      case 5: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 5>(D, L, b, t, feas, xreg, ureg, cur, stamp, red5); break;
-      case 6: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 6>(D, L, b, t, feas, xreg, ureg, cur, stamp, red5); break;
-      default: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 7>(D, L, b, t, feas, xreg, ureg, cur, stamp, red5); break;
+      case 0: ok = bwd_knot<NTL, MTL, NW, 0>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 1: ok = bwd_knot<NTL, MTL, NW, 1>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 2: ok = bwd_knot<NTL, MTL, NW, 2>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 3: ok = bwd_knot<NTL, MTL, NW, 3>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 4: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 4>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 5: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 5>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 6: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 6>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      default: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 7>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
     }
     if (!ok) {  // the factorisation failed (every wave saw the flag)
       stamp.flush();
@@ -1436,8 +1438,9 @@ __device__ __forceinline__ bool bwd_sweep_mfma(const Dev& D, int b, bool feas, d
   // ei = {dg, dq, stop}, in thread 0
   if constexpr (Cfg::ct_own) {  // the running sums over the workgroup
     wg_sums<NT, 5>(red5, L.red);
-    ei[0] = feas ? red5[0] : red5[0] - red5[2];
-    ei[1] = feas ? -red5[1] : red5[3] - red5[1];
+    // (ddp: SolverDDP::expectedImprovement, ddp.cpp:144-155, has no gap terms)
+    ei[0] = feas || ddp ? red5[0] : red5[0] - red5[2];
+    ei[1] = feas || ddp ? -red5[1] : red5[3] - red5[1];
     ei[2] = red5[4];
   }  // (else: the per-knot sums in D.part, summed by the kernel's epilogue)
   return true;
@@ -1455,66 +1458,90 @@ constexpr size_t bwd_lds_bytes() {
 
 // (the four-wave plans at two waves per SIMD: two workgroups per CU, which is what the
 // residency-based plan choice counts on)
+// The kernel's body, for a compile-time DDPM: the DDP solver kinds compiled in (Prm::ddp: d_ without
+// gap terms; Dev::box == 2: SolverBoxDDP's QP on infeasible candidates). Without it both are
+// compile-time false and the kernel is SolverFDDP / SolverBoxFDDP's alone. A macro, so that the
+// kernels below keep their statements in the __global__ function itself, as the one kernel had them
+// (through an inlined function the 5 x 2 x 8 kernel's register allocation came out differently).
+#define FDDP_BACKWARD_MFMA_BODY(DDPM) \
+  const int b = blockIdx.x;                                                                  \
+  ElemState* st = D.st + b;                                                                  \
+  if (mode == 0 && !st->active) return;                                                      \
+  extern __shared__ __attribute__((aligned(16))) double sm[];                                \
+  const bool feas = st->is_feasible != 0;                                                    \
+  const bool ddp = DDPM && prm.ddp != 0;                                                     \
+  const bool boxqp = DDPM ? feas || D.box > 1 : feas;                                        \
+  double xreg = st->xreg, ureg = st->ureg;                                                   \
+  bool ok;                                                                                   \
+  int tries = 0;                                                                             \
+  const int max_tries = reg_retry_bound(prm, xreg);                                          \
+  double ei[3];  /* dg, dq, stop (thread 0) */                                               \
+  for (;;) {                                                                                 \
+    ok = bwd_sweep_mfma<NTL, MTL, NW>(D, b, feas, boxqp, xreg, ureg, st->cur, sm, ei, ddp);  \
+    __syncthreads();                                                                         \
+    if (ok || mode == 1) break;                                                              \
+    xreg *= prm.regfactor;  /* increaseRegularization (ddp.cpp:312-318) */                   \
+    if (xreg > prm.regmax) xreg = prm.regmax;                                                \
+    ureg = xreg;                                                                             \
+    /* (as the reference: at regmax; a NaN / zero xreg never reaches it: the bound */        \
+    /* reg_retry_bound makes every wave of the workgroup leave the loop) */                  \
+    if (!(xreg < prm.regmax) || ++tries >= max_tries) break;                                 \
+  }                                                                                          \
+  if (threadIdx.x == 0) {                                                                    \
+    st->xreg = xreg;                                                                         \
+    st->ureg = ureg;                                                                         \
+    st->bwd_fail = ok ? 0 : 1;                                                               \
+    if (!ok && mode == 0) {                                                                  \
+      st->status = FDDP_STATUS_REGMAX;                                                       \
+      st->active = 0;                                                                        \
+      st->n_iter_run += 1;                                                                   \
+    }                                                                                        \
+    if (ok) {                                                                                \
+      if constexpr (!MfmaCfg<NTL, MTL>::ct_own) {  /* the per-knot sums, in knot order */    \
+        const double* p = D.part + D.knot(b, 0) * 8;                                         \
+        const int T = D.T;                                                                   \
+        double dg = 0., dq = 0., stop = 0.;                                                  \
+        const bool gap = !feas && !ddp;  /* (SolverDDP's d_ has no gap terms) */             \
+        if (gap) {                                                                           \
+          dg -= p[T * 8 + 2];                                                                \
+          dq += p[T * 8 + 3];                                                                \
+        }                                                                                    \
+        for (int t = 0; t < T; ++t) {                                                        \
+          dg += p[t * 8 + 0];                                                                \
+          dq -= p[t * 8 + 1];                                                                \
+          stop += p[t * 8 + 4];                                                              \
+          if (gap) {                                                                         \
+            dg -= p[t * 8 + 2];                                                              \
+            dq += p[t * 8 + 3];                                                              \
+          }                                                                                  \
+        }                                                                                    \
+        ei[0] = dg;                                                                          \
+        ei[1] = dq;                                                                          \
+        ei[2] = stop;                                                                        \
+      }                                                                                      \
+      st->dg = ei[0];                                                                        \
+      st->dq = ei[1];                                                                        \
+      st->stop = ei[2];                                                                      \
+    }                                                                                        \
+  }                                                                                          \
+
+// The Talos-size plan (5 x 2 tiles, eight waves) runs at the register cap with spills: its kernel is
+// built without the DDP kinds, so SolverFDDP's sweep there is the code it was, and a DDP / BoxDDP
+// handle runs the same plan from a kernel of its own (backward_mfma_ddp_kernel; ktab::backward_mfma
+// picks by Prm::ddp / Dev::box). The small plans carry the kinds as uniform branches.
+template <int NTL, int MTL, int NW>
+constexpr bool kBwdDdpInline = !(NTL == 5 && MTL == 2 && NW == 8);
+
 template <int NTL, int MTL, int NW>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4 ? 2 : 1))) void backward_mfma_kernel(
     Dev D, Prm prm, int mode) {
-  const int b = blockIdx.x;
-  ElemState* st = D.st + b;
-  if (mode == 0 && !st->active) return;
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  const bool feas = st->is_feasible != 0;
-  double xreg = st->xreg, ureg = st->ureg;
-  bool ok;
-  int tries = 0;
-  const int max_tries = reg_retry_bound(prm, xreg);
-  double ei[3];  // dg, dq, stop (thread 0)
-  for (;;) {
-    ok = bwd_sweep_mfma<NTL, MTL, NW>(D, b, feas, xreg, ureg, st->cur, sm, ei);
-    __syncthreads();
-    if (ok || mode == 1) break;
-    xreg *= prm.regfactor;  // increaseRegularization (ddp.cpp:312-318)
-    if (xreg > prm.regmax) xreg = prm.regmax;
-    ureg = xreg;
-    // (as the reference: at regmax; a NaN / zero xreg never reaches it: the bound
-    // reg_retry_bound makes every wave of the workgroup leave the loop)
-    if (!(xreg < prm.regmax) || ++tries >= max_tries) break;
-  }
-  if (threadIdx.x == 0) {
-    st->xreg = xreg;
-    st->ureg = ureg;
-    st->bwd_fail = ok ? 0 : 1;
-    if (!ok && mode == 0) {
-      st->status = FDDP_STATUS_REGMAX;
-      st->active = 0;
-      st->n_iter_run += 1;
-    }
-    if (ok) {
-      if constexpr (!MfmaCfg<NTL, MTL>::ct_own) {  // the per-knot sums, in knot order
-        const double* p = D.part + D.knot(b, 0) * 8;
-        const int T = D.T;
-        double dg = 0., dq = 0., stop = 0.;
-        if (!feas) {
-          dg -= p[T * 8 + 2];
-          dq += p[T * 8 + 3];
-        }
-        for (int t = 0; t < T; ++t) {
-          dg += p[t * 8 + 0];
-          dq -= p[t * 8 + 1];
-          stop += p[t * 8 + 4];
-          if (!feas) {
-            dg -= p[t * 8 + 2];
-            dq += p[t * 8 + 3];
-          }
-        }
-        ei[0] = dg;
-        ei[1] = dq;
-        ei[2] = stop;
-      }
-      st->dg = ei[0];
-      st->dq = ei[1];
-      st->stop = ei[2];
-    }
-  }
+  constexpr bool kDdp = kBwdDdpInline<NTL, MTL, NW>;
+  FDDP_BACKWARD_MFMA_BODY(kDdp)
+}
+template <int NTL, int MTL, int NW>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4 ? 2 : 1))) void backward_mfma_ddp_kernel(
+    Dev D, Prm prm, int mode) {
+  FDDP_BACKWARD_MFMA_BODY(true)
 }
 
 }  // namespace fddp

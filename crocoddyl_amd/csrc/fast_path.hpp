@@ -543,15 +543,15 @@ __global__ __launch_bounds__(NT) void calc_tiled_kernel(Dev D, int sel_calc, int
 // the in-order running sum and the NaN checks run once at the end.
 // ---------------------------------------------------------------------------
 template <int NT, bool FAST>
-__device__ __forceinline__ bool fwd_trial_fast(const Dev& D, int b, const ElemState& s, double alpha, double* xu,
-                                               double* dxv, double* xn, double* pa, double* pdyn, double* red,
-                                               int* flag, double& cost_try, double& dv, double* pl, int64_t pcap,
-                                               const double*& cached) {
+__device__ __forceinline__ bool fwd_trial_fast(const Dev& D, int b, const ElemState& s, bool ddp, double alpha,
+                                               double* xu, double* dxv, double* xn, double* pa, double* pdyn,
+                                               double* red, int* flag, double& cost_try, double& dv, double* pl,
+                                               int64_t pcap, const double*& cached) {
   const int n = D.n, nx = D.nx, m = D.m, T = D.T, tid = threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
   constexpr int NW = NT / 64;
   const int c = s.cur, o = 1 - c;
-  const bool feas = s.is_feasible != 0;
+  const bool feas = ddp || s.is_feasible != 0;  // (ddp: SolverDDP's rollout, as fwd_trial)
   const bool full = feas || alpha == 1.;
   const double* x0 = D.x0 + (int64_t)b * D.sX;
   if (tid < nx) xn[tid] = x0[tid];

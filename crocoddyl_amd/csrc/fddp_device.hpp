@@ -211,7 +211,8 @@ struct Dev {
   unsigned long long* stamps;  // diagnostic: [B][4 waves][8 phases] cycles (null = off)
   // SolverBoxFDDP (box-fddp.cpp:15-160): box QP gains on limited knots once
   // feasible, clamped controls in the forward pass
-  int box;                         // solver kind == FDDP_SOLVER_BOXFDDP
+  int box;                         // 1: solver kind FDDP_SOLVER_BOXFDDP; 2: FDDP_SOLVER_BOXDDP (box-ddp.cpp: the
+                                   // box QP gains on an infeasible candidate too)
   const double *ulb, *uub;         // [B][T][sM] control limits (null = none set)
   const unsigned char* haslim;     // [B][T] has_control_limits (null = none)
   double* dQuuInv;                 // debug [B][T][sMM] Quu_inv_ (null unless debug + box)
@@ -248,6 +249,10 @@ struct Prm {
   double th_acceptstep, th_stop, th_grad, th_stepdec, th_stepinc, th_acceptnegstep;
   double regfactor, regmin, regmax;
   int n_alphas;
+  // solver kind FDDP_SOLVER_DDP / _BOXDDP (ddp.cpp): the rollout closes no gap at any alpha,
+  // d_ carries no gap terms, the acceptance rule is SolverDDP::solve's and an accepted
+  // iterate is feasible. A kernel argument, so uniform over the launch (scalar registers).
+  int ddp;
   double alphas[16];
 };
 

@@ -281,8 +281,13 @@ struct Timed {
   }
 };
 
-Prm to_prm(const fddp_params& p) {
+inline bool ddp_kind(int kind) { return kind == FDDP_SOLVER_DDP || kind == FDDP_SOLVER_BOXDDP; }
+
+// the thresholds of a handle with its solver kind's line-search rule (Prm::ddp)
+Prm to_prm(const fddp_handle* h) {
+  const fddp_params& p = h->prm;
   Prm q;
+  q.ddp = ddp_kind(h->solver_kind) ? 1 : 0;
   q.th_acceptstep = p.th_acceptstep;
   q.th_stop = p.th_stop;
   q.th_grad = p.th_grad;
@@ -388,9 +393,9 @@ int launch_backward(fddp_handle* h, int mode) {
   Timed tm(h, 2);
   const Dev& D = h->D;
   if (h->plan.var.bwd)
-    KLAUNCH(ktab::backward_mfma(h->plan.var.bwd, dim3(D.B), h->stream, D, to_prm(h->prm), mode));
+    KLAUNCH(ktab::backward_mfma(h->plan.var.bwd, dim3(D.B), h->stream, D, to_prm(h), mode));
   else
-    KLAUNCH(ktab::backward_generic(dim3(D.B), h->bwd_smem, h->stream, D, to_prm(h->prm), mode));
+    KLAUNCH(ktab::backward_generic(dim3(D.B), h->bwd_smem, h->stream, D, to_prm(h), mode));
   return FDDP_OK;
 }
 
@@ -505,11 +510,11 @@ int launch_forward(fddp_handle* h, int mode, double alpha, int* count) {
     const int na = h->prm.n_alphas, G = (na + D.npar - 1) / D.npar;
     h->ls_npar_last = D.npar;
     h->ls_launches_last = G;
-    const int v = h->plan.var.fwd;
+    const int v = plan::rollout_for_kind(h->plan.var.fwd, h->solver_kind);
     for (int g = 0; g < G; ++g) {
-      KLAUNCH(ktab::forward(v, dim3(D.B, D.npar), h->plan.lds.fwd_smem, h->stream, D, to_prm(h->prm), 2, 1., nullptr, h->plan.lds.pcap,
+      KLAUNCH(ktab::forward(v, dim3(D.B, D.npar), h->plan.lds.fwd_smem, h->stream, D, to_prm(h), 2, 1., nullptr, h->plan.lds.pcap,
                             g));
-      KLAUNCH(ktab::ls_select(dim3(D.B), h->stream, D, to_prm(h->prm), g, g == G - 1 ? 1 : 0, count));
+      KLAUNCH(ktab::ls_select(dim3(D.B), h->stream, D, to_prm(h), g, g == G - 1 ? 1 : 0, count));
     }
     return FDDP_OK;
   }
@@ -518,11 +523,11 @@ int launch_forward(fddp_handle* h, int mode, double alpha, int* count) {
     h->ls_launches_last = 1;
   }
   if (h->plan.lds.fast)
-    KLAUNCH(ktab::forward(ktab::FWD_FAST, dim3(D.B), h->plan.lds.fwd_fast_smem, h->stream, D, to_prm(h->prm), mode, alpha,
+    KLAUNCH(ktab::forward(ktab::FWD_FAST, dim3(D.B), h->plan.lds.fwd_fast_smem, h->stream, D, to_prm(h), mode, alpha,
                           count, h->plan.lds.pcap, 0));
   else
-    KLAUNCH(ktab::forward(h->plan.var.fwd, dim3(D.B), h->plan.lds.fwd_smem, h->stream, D,
-                          to_prm(h->prm), mode, alpha, count, h->plan.lds.pcap, 0));
+    KLAUNCH(ktab::forward(plan::rollout_for_kind(h->plan.var.fwd, h->solver_kind), dim3(D.B), h->plan.lds.fwd_smem, h->stream, D,
+                          to_prm(h), mode, alpha, count, h->plan.lds.pcap, 0));
   return FDDP_OK;
 }
 
@@ -530,12 +535,13 @@ __global__ void set_feasible_kernel(Dev D, int is_feasible) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < D.B) D.st[b].is_feasible = is_feasible;
 }
-__global__ void ei_kernel(Dev D, double* out) {
+__global__ void ei_kernel(Dev D, double* out, int ddp) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= D.B) return;
   ElemState& s = D.st[b];
-  s.d0 = s.dg + s.dv;
-  s.d1 = s.dq - 2 * s.dv;
+  // (ddp: SolverDDP::expectedImprovement, ddp.cpp:144-155, does not depend on the trial)
+  s.d0 = ddp ? s.dg : s.dg + s.dv;
+  s.d1 = ddp ? s.dq : s.dq - 2 * s.dv;
   out[2 * b] = s.d0;
   out[2 * b + 1] = s.d1;
 }
@@ -1152,7 +1158,7 @@ int fddp_get_kernel_info(fddp_handle* h, int32_t out[8]) {
   if (!h || !out) return fail(FDDP_ERR_INVALID_ARG, "fddp_get_kernel_info: null argument");
   DeviceGuard g(h->device);
   out[0] = h->plan.var.mb;
-  out[1] = h->plan.var.fwd;
+  out[1] = plan::rollout_for_kind(h->plan.var.fwd, h->solver_kind);
   out[2] = h->plan.var.bwd;
   out[3] = h->D.mbspill;
   out[4] = (int32_t)h->plan.lds.mb_diff_smem;
@@ -1315,7 +1321,8 @@ int fddp_expected_improvement(fddp_handle* h, double* d) {
   if (!h) return fail(FDDP_ERR_INVALID_ARG, "null handle");
   DeviceGuard g(h->device);
   const Dev& D = h->D;
-  hipLaunchKernelGGL(ei_kernel, dim3((D.B + 255) / 256), dim3(256), 0, h->stream, D, h->d_out);
+  hipLaunchKernelGGL(ei_kernel, dim3((D.B + 255) / 256), dim3(256), 0, h->stream, D, h->d_out,
+                     ddp_kind(h->solver_kind) ? 1 : 0);
   LAUNCH_CHECK();
   if (d) HIP_TRY(hipMemcpyAsync(d, h->d_out, sizeof(double) * 2 * D.B, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1439,12 +1446,12 @@ int fddp_set_knots(fddp_handle* h, const fddp_knot_desc* knots, const double* pa
 
 int fddp_set_solver_kind(fddp_handle* h, int kind) {
   if (!h) return fail(FDDP_ERR_INVALID_ARG, "fddp_set_solver_kind: null handle");
-  if (kind != FDDP_SOLVER_FDDP && kind != FDDP_SOLVER_BOXFDDP)
+  if (kind != FDDP_SOLVER_FDDP && kind != FDDP_SOLVER_BOXFDDP && kind != FDDP_SOLVER_DDP && kind != FDDP_SOLVER_BOXDDP)
     return fail(FDDP_ERR_INVALID_ARG, "fddp_set_solver_kind: unknown solver kind");
-  if (kind == FDDP_SOLVER_BOXFDDP && h->dims.nu_max > 64)
+  if ((kind == FDDP_SOLVER_BOXFDDP || kind == FDDP_SOLVER_BOXDDP) && h->dims.nu_max > 64)
     return fail(FDDP_ERR_UNSUPPORTED, "fddp_set_solver_kind: the box QP holds at most 64 controls (one wave)");
   h->solver_kind = kind;
-  h->D.box = kind == FDDP_SOLVER_BOXFDDP ? 1 : 0;
+  h->D.box = kind == FDDP_SOLVER_BOXFDDP ? 1 : (kind == FDDP_SOLVER_BOXDDP ? 2 : 0);
   return FDDP_OK;
 }
 

@@ -530,8 +530,9 @@ __device__ __forceinline__ bool bwd_sweep(const Dev& D, int b, bool feas, double
       for (int e = tid; e < m * m; e += NT) D.dQuu[r * D.sMM + e] = (e % m < nu && e / m < nu) ? S.Quu[e] : 0.;
     }
     __syncthreads();
-    if (nu && feas && D.box_knot(b, t)) {
-      // box QP gains; K = Quu_inv Qxu^T (S.A, nu x n, ld m)
+    if (nu && (feas || D.box > 1) && D.box_knot(b, t)) {
+      // box QP gains (SolverBoxDDP, D.box == 2: on an infeasible candidate too, box-ddp.cpp:44-75);
+      // K = Quu_inv Qxu^T (S.A, nu x n, ld m)
       if (tid < 64 && !box_gains_generic(D, S, S.L, b, t, cur, tid) && tid == 0) *S.flag = 1;
       __syncthreads();
       if (*S.flag) return false;
@@ -705,7 +706,9 @@ __global__ __launch_bounds__(NT) void backward_kernel(Dev D, Prm prm, int mode) 
       const double* p = D.part + D.knot(b, 0) * 8;
       const int T = D.T;
       double dg = 0., dq = 0., stop = 0.;
-      if (!feas) {
+      // (SolverDDP::expectedImprovement, ddp.cpp:144-155: no gap terms)
+      const bool gap = !feas && !prm.ddp;
+      if (gap) {
         dg -= p[T * 8 + 2];
         dq += p[T * 8 + 3];
       }
@@ -715,7 +718,7 @@ __global__ __launch_bounds__(NT) void backward_kernel(Dev D, Prm prm, int mode) 
           dq -= p[t * 8 + 1];
           stop += p[t * 8 + 4];
         }
-        if (!feas) {
+        if (gap) {
           dg -= p[t * 8 + 2];
           dq += p[t * 8 + 3];
         }
@@ -789,13 +792,15 @@ __device__ __forceinline__ double gains_dot(const double* K, int m, int i, int n
 }
 
 template <int NT, bool MB = false>
-__device__ __forceinline__ bool fwd_trial(const Dev& D, int b, const ElemState& s, double alpha, double* xv, double* uv, double* xn,
+__device__ __forceinline__ bool fwd_trial(const Dev& D, int b, const ElemState& s, bool ddp, double alpha, double* xv, double* uv, double* xn,
                           double* red, int* flag, double& cost_try, double& dv, double* pl, int64_t pcap,
                           const double*& cached, double* mbw, double* dxv, int slot = 0, int* nwritten = nullptr) {
   const int n = D.n, nx = D.nx, m = D.m, T = D.T, tid = threadIdx.x;
   const int c = s.cur, o = 1 - c;
   const TrialOut out(D, o, slot);
-  const bool feas = s.is_feasible != 0;
+  // ddp: SolverDDP::forwardPass (ddp.cpp:255-296) closes no gap at any alpha: the rollout of a
+  // feasible candidate, whatever the element's flag
+  const bool feas = ddp || s.is_feasible != 0;
   const bool full = feas || alpha == 1.;
   const bool ff = nx != n;  // free-flyer state (dxv: 2 sN doubles of LDS)
   const double* x0 = D.x0 + (int64_t)b * D.sX;
@@ -941,10 +946,10 @@ __device__ __forceinline__ bool fwd_trial(const Dev& D, int b, const ElemState& 
 }
 
 template <int NT, bool FAST>
-__device__ __forceinline__ bool fwd_trial_fast(const Dev& D, int b, const ElemState& s, double alpha, double* xu,
-                                               double* dxv, double* xn, double* pa, double* pdyn, double* red,
-                                               int* flag, double& cost_try, double& dv, double* pl, int64_t pcap,
-                                               const double*& cached);
+__device__ __forceinline__ bool fwd_trial_fast(const Dev& D, int b, const ElemState& s, bool ddp, double alpha,
+                                               double* xu, double* dxv, double* xn, double* pa, double* pdyn,
+                                               double* red, int* flag, double& cost_try, double& dv, double* pl,
+                                               int64_t pcap, const double*& cached);
 
 // Forward-pass LDS beyond the parameter block (doubles): generic trial
 // [xv sX | uv sM | xn sX | red 5*NW+8 | flag 2 | dxv 2 sN | multibody scratch D.mbw_fwd], fast trial
@@ -956,7 +961,13 @@ __host__ __device__ inline int64_t fwd_lds_doubles(int64_t sX, int64_t sN, int64
 
 // The line search's test of one finished trial (fddp.cpp:57-78): fills the
 // trial's bookkeeping into s; true if alpha is accepted (then s holds the new state).
+// DDP (with prm.ddp): SolverDDP::solve's rule (ddp.cpp:76-89). Its trials return dv = 0 and the
+// sweep left the gap terms out of dg / dq, so d_ and dVexp below are expectedImprovement()'s;
+// no step is accepted at dVexp < 0, any at dVexp >= 0 while infeasible, and the accepted
+// iterate is feasible (setCandidate(xs_try_, us_try_, true)).
+template <bool DDP = true>
 __device__ __forceinline__ bool ls_accept(const Prm& prm, ElemState& s, double alpha, double ct, double dv) {
+  const bool ddp = DDP && prm.ddp;
   s.cost_try = ct;
   s.dV = s.cost - ct;
   s.dv = dv;
@@ -965,12 +976,12 @@ __device__ __forceinline__ bool ls_accept(const Prm& prm, ElemState& s, double a
   s.dVexp = alpha * (s.d0 + 0.5 * alpha * s.d1);
   bool acc;
   if (s.dVexp >= 0)
-    acc = s.d0 < prm.th_grad || s.dV > prm.th_acceptstep * s.dVexp;
+    acc = s.d0 < prm.th_grad || (ddp && !s.is_feasible) || s.dV > prm.th_acceptstep * s.dVexp;
   else
-    acc = s.dV > prm.th_acceptnegstep * s.dVexp;
+    acc = !ddp && s.dV > prm.th_acceptnegstep * s.dVexp;
   if (acc) {
     s.was_feasible = s.is_feasible;
-    s.is_feasible = (s.was_feasible || alpha == 1.) ? 1 : 0;
+    s.is_feasible = (s.was_feasible || alpha == 1. || ddp) ? 1 : 0;
     s.cur = 1 - s.cur;
     s.cost = ct;
   }
@@ -1025,6 +1036,11 @@ __device__ __forceinline__ void ls_finish(const Prm& prm, ElemState& s, bool acc
 // whole register file: under the 2-waves cap its spills trip a backend error)
 // MBW: waves per EU of the multibody variant (3: three workgroups per CU where the LDS
 // allows it, at 168 VGPRs; 2: the 256-VGPR build for batches that fit two per CU anyway)
+// The MBW = 3 build runs at its register cap with spills: the DDP mode of the line search
+// (Prm::ddp) is compiled out of it, so SolverFDDP's rollout there is the code it was.
+#ifndef FDDP_FWD_DDP_MB3
+#define FDDP_FWD_DDP_MB3 0
+#endif
 template <int NT, bool FAST, bool MB = false, int MBW = FDDP_FWD_WPE_MB>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MB ? MBW : FAST ? FDDP_FWD_WPE : 1))) void forward_kernel(Dev D, Prm prm, int mode, double alpha1, int* active_count,
                                                      int64_t pcap, int group = 0) {
@@ -1079,11 +1095,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MB ? MBW : F
   // the gains' K staging stays below it (fddp_create checks the room)
   double* const mbw = (double*)flag + 2 + (D.dxv_mbw ? 0 : 2 * D.sN);
   double* const dxv_ = D.dxv_mbw ? mbw + D.mbw_fwd - 2 * D.sN : (double*)flag + 2;
+  // (the three-workgroups-per-CU multibody build has no DDP mode, FDDP_FWD_DDP_MB3:
+  // plan::rollout_for_kind sends a DDP handle to the two-workgroup build)
+  constexpr bool kDdp = !(MB && MBW == 3) || FDDP_FWD_DDP_MB3;
+  const bool ddp = kDdp && prm.ddp;
   auto trial = [&](double alpha, double& ct, double& dv) {
     if constexpr (FAST)
-      return fwd_trial_fast<NT, true>(D, b, ss, alpha, xv, dxv, xn, pa, pdyn, red, flag, ct, dv, pl, pcap, cached);
+      return fwd_trial_fast<NT, true>(D, b, ss, ddp, alpha, xv, dxv, xn, pa, pdyn, red, flag, ct, dv, pl, pcap, cached);
     else
-      return fwd_trial<NT, MB>(D, b, ss, alpha, xv, uv, xn, red, flag, ct, dv, pl, pcap, cached, mbw, dxv_, slot, &nwr);
+      return fwd_trial<NT, MB>(D, b, ss, ddp, alpha, xv, uv, xn, red, flag, ct, dv, pl, pcap, cached, mbw, dxv_, slot, &nwr);
   };
   // line search (fddp.cpp:53-81). One call site of the trial, so it is inlined (its
   // LDS pointers keep their address space).
@@ -1115,7 +1135,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MB ? MBW : F
     }
     ElemState s = ss;
     s.steplength = alpha;
-    const bool acc = ok && ls_accept(prm, s, alpha, ct, dv);
+    const bool acc = ok && ls_accept<kDdp>(prm, s, alpha, ct, dv);
     __syncthreads();  // (every thread has read ss)
     if (threadIdx.x == 0) ss = s;
     __syncthreads();

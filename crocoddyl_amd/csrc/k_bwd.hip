@@ -1,12 +1,14 @@
 // Riccati sweep kernels (bwd_mfma.hpp backward_mfma_kernel, fddp_kernels.hpp
 // backward_kernel). FDDP_TU_BWD = 0: the C5-sized MFMA variant (5 x 2 tiles); 1: the
-// other MFMA variants and the generic VALU sweep.
+// other MFMA variants and the generic VALU sweep; 2: the C5-sized variant's build with the
+// DDP solver kinds (an object of its own: kernels compiled together share the register
+// allocator's context, and SolverFDDP's C5 sweep is to stay the code it was).
 #include "bwd_mfma.hpp"
 #include "fddp_kernels.hpp"
 #include "ktab.hpp"
 
 #ifndef FDDP_TU_BWD
-#error "k_bwd.hip is compiled with -DFDDP_TU_BWD=0|1"
+#error "k_bwd.hip is compiled with -DFDDP_TU_BWD=0|1|2"
 #endif
 
 namespace fddp {
@@ -20,6 +22,8 @@ int setup_one(int n, int* per_cu) {
   if (lds > 160 * 1024 || n > Cfg::ZLD) return -1;
   const void* f = (const void*)backward_mfma_kernel<NTL, MTL, NW>;
   if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+  if constexpr (!kBwdDdpInline<NTL, MTL, NW>)  // the DDP kinds' kernel of this plan: the same LDS
+    if (backward_mfma_ddp_setup_2((int)lds) != hipSuccess) return -1;
   // resident workgroups per CU (registers and LDS): the plan choice weighs it
   if (per_cu && hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f, NW * 64, lds) != hipSuccess) *per_cu = 1;
   // column-block ownership per wave is static (BwdPlan in bwd_mfma.hpp)
@@ -27,6 +31,12 @@ int setup_one(int n, int* per_cu) {
 }
 template <int NTL, int MTL, int NW>
 void launch_one(dim3 grid, hipStream_t s, const Dev& D, const Prm& prm, int mode) {
+  if constexpr (!kBwdDdpInline<NTL, MTL, NW>) {
+    if (prm.ddp || D.box > 1) {  // SolverDDP / SolverBoxDDP: the build of this plan that has the kinds
+      backward_mfma_ddp_2(grid, s, D, prm, mode);
+      return;
+    }
+  }
   backward_mfma_kernel<NTL, MTL, NW><<<grid, dim3(NW * 64), bwd_lds_bytes<NTL, MTL, NW>(), s>>>(D, prm, mode);
 }
 }  // namespace
@@ -39,6 +49,13 @@ hipError_t backward_mfma_0(int code, dim3 grid, hipStream_t s, const Dev& D, con
   if (code != 528) return hipErrorInvalidDeviceFunction;
   launch_one<5, 2, 8>(grid, s, D, prm, mode);
   return hipGetLastError();
+}
+#elif FDDP_TU_BWD == 2
+hipError_t backward_mfma_ddp_setup_2(int lds) {
+  return hipFuncSetAttribute((const void*)backward_mfma_ddp_kernel<5, 2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+}
+void backward_mfma_ddp_2(dim3 grid, hipStream_t s, const Dev& D, const Prm& prm, int mode) {
+  backward_mfma_ddp_kernel<5, 2, 8><<<grid, dim3(8 * 64), bwd_lds_bytes<5, 2, 8>(), s>>>(D, prm, mode);
 }
 #else
 int backward_mfma_setup_1(int ntl, int mtl, int nw, int n, int* per_cu) {  // -1: no such variant or it does not fit

@@ -87,6 +87,9 @@ int backward_mfma_setup_0(int ntl, int mtl, int nw, int n, int* per_cu);  // -2:
 int backward_mfma_setup_1(int ntl, int mtl, int nw, int n, int* per_cu);
 hipError_t backward_mfma_0(int code, dim3 grid, hipStream_t s, const Dev& D, const Prm& prm, int mode);
 hipError_t backward_mfma_1(int code, dim3 grid, hipStream_t s, const Dev& D, const Prm& prm, int mode);
+// the 5 x 2 x 8 plan's kernel with the DDP solver kinds (SolverDDP / SolverBoxDDP handles)
+hipError_t backward_mfma_ddp_setup_2(int lds);
+void backward_mfma_ddp_2(dim3 grid, hipStream_t s, const Dev& D, const Prm& prm, int mode);
 }  // namespace ktab
 }  // namespace fddp
 

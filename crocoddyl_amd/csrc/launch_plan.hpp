@@ -555,6 +555,16 @@ inline VariantPlan plan_variants(const LdsPlan& l, const fddp_dims& d, const Ove
   return v;
 }
 
+// The rollout variant a launch takes under the handle's solver kind (fddp_set_solver_kind
+// switches kinds on a live handle, so this is asked at every launch, not planned): the
+// three-workgroups-per-CU multibody build has no DDP mode compiled in (fddp_kernels.hpp
+// FDDP_FWD_DDP_MB3), so a DDP / BoxDDP handle planned onto it rolls out with the
+// two-workgroup build, which takes the same dynamic LDS. Every other variant has the mode.
+inline int rollout_for_kind(int fwd, int solver_kind) {
+  const bool ddp = solver_kind == FDDP_SOLVER_DDP || solver_kind == FDDP_SOLVER_BOXDDP;
+  return ddp && fwd == ktab::FWD_MB && !FDDP_FWD_DDP_MB3 ? ktab::FWD_MB2 : fwd;
+}
+
 }  // namespace plan
 }  // namespace fddp
 

@@ -328,6 +328,14 @@ class HostSolverFDDP:
         self.forwardPass(stepLength)
         return self.cost - self.cost_try
 
+    def _accepts(self):  # fddp.cpp:62-78, on the trial's dV, d and dVexp
+        if self.dVexp >= 0:
+            return self.d[0] < self.th_grad or self.dV > self.th_acceptstep * self.dVexp
+        return self.dV > self.th_acceptnegstep * self.dVexp
+
+    def _feasible_after(self, a):  # fddp.cpp:66, 74
+        return self.was_feasible or a == 1
+
     def solve(self, init_xs=[], init_us=[], maxiter=100, isFeasible=False, regInit=1e-9):
         pb = self.problem
         self.xs_try[0] = pb._x0b[0].copy()
@@ -356,14 +364,10 @@ class HostSolverFDDP:
                     continue
                 self.expectedImprovement()
                 self.dVexp = a * (self.d[0] + 0.5 * a * self.d[1])
-                if self.dVexp >= 0:
-                    accept = self.d[0] < self.th_grad or self.dV > self.th_acceptstep * self.dVexp
-                else:
-                    accept = self.dV > self.th_acceptnegstep * self.dVexp
-                if accept:
+                if self._accepts():
                     self.was_feasible = self.isFeasible
                     self.setCandidate([x.copy() for x in self.xs_try], [u.copy() for u in self.us_try],
-                                      self.was_feasible or a == 1)
+                                      self._feasible_after(a))
                     self.cost = self.cost_try
                     recalc = True
                     break
@@ -380,3 +384,35 @@ class HostSolverFDDP:
                 return True
         self.iter = maxiter
         return False
+
+
+class HostSolverDDP(HostSolverFDDP):
+    """SolverDDP (ddp.cpp:39-310) for a host-mode problem: SolverFDDP's loop with a rollout
+    that closes no gap, an expected improvement without gap terms, SolverDDP::solve's
+    acceptance rule, and a feasible iterate after any accepted step."""
+
+    def forwardPass(self, steplength):  # ddp.cpp:255-296: SolverFDDP's rollout of a feasible candidate
+        feas, self.isFeasible = self.isFeasible, True
+        try:
+            super().forwardPass(steplength)
+        finally:
+            self.isFeasible = feas
+
+    def updateExpectedImprovement(self):  # the sums of ddp.cpp:144-155
+        self.dg = self.dq = 0.0
+        for t, m in enumerate(self.problem._models):
+            if m.nu:
+                self.dg += float(self.Qu[t] @ self.k[t])
+                self.dq -= float(self.k[t] @ self.Quuk[t])
+
+    def expectedImprovement(self):  # ddp.cpp:144-155: no dependence on the trial
+        self.dv = 0.0
+        self.d = np.array([self.dg, self.dq])
+        return self.d
+
+    def _accepts(self):  # ddp.cpp:76-89; th_acceptnegstep is unused
+        return self.dVexp >= 0 and (self.d[0] < self.th_grad or not self.isFeasible
+                                    or self.dV > self.th_acceptstep * self.dVexp)
+
+    def _feasible_after(self, a):  # setCandidate(xs_try_, us_try_, true)
+        return True

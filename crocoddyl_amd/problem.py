@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _abi
 from ._lib import FDDPError, check, default_params, lib
-from .host import HostProblem, HostSolverFDDP, is_host_model
+from .host import HostProblem, HostSolverDDP, HostSolverFDDP, is_host_model
 from .models import ActionData, ActionModelAbstract
 
 
@@ -437,12 +437,15 @@ class SolverFDDP:
     """SolverFDDP (src/core/solvers/fddp.cpp) on the device, batched. A problem with
     Python-defined action models gets the host solver (host.HostSolverFDDP)."""
 
+    _host_solver = HostSolverFDDP  # the host loop of this class itself (subclasses: None unless they set one)
+
     def __new__(cls, problem):
         if getattr(problem, "host_mode", False):
-            if cls is not SolverFDDP:
+            host = cls.__dict__.get("_host_solver")
+            if host is None:
                 raise NotImplementedError(f"crocoddyl_amd: {cls.__name__} needs device models (Python-defined "
-                                          "action models run with SolverFDDP)")
-            return HostSolverFDDP(problem)
+                                          "action models run with SolverFDDP or SolverDDP)")
+            return host(problem)
         return super().__new__(cls)
 
     def __init__(self, problem):
@@ -838,3 +841,35 @@ class SolverBoxFDDP(SolverFDDP):
         before the backward pass (device-side store)."""
         p = self.problem
         return self._quantity(_abi.Q_QUU_INV, p.T, p.nu_max, p.nu_max, "both")
+
+
+class SolverDDP(SolverFDDP):
+    """SolverDDP (src/core/solvers/ddp.cpp:39-310) on the device, batched: the same
+    calcDiff and backward pass as SolverFDDP; the rollout closes no gap at any step
+    length, ``d`` carries no gap terms, a step is accepted only at dVexp >= 0, and the
+    iterate is feasible after any accepted step (fddp_hip.h FDDP_SOLVER_DDP). It shares
+    SolverFDDP's API by inheritance (the reference derives the other way round). A
+    problem with Python-defined action models gets the host loop (host.HostSolverDDP)."""
+
+    _host_solver = HostSolverDDP
+    _kind = _abi.SOLVER_DDP
+
+    def __init__(self, problem):
+        super().__init__(problem)
+        check(lib().fddp_set_solver_kind(self._h.ptr, self._kind))
+
+
+class SolverBoxDDP(SolverDDP):
+    """SolverBoxDDP (src/core/solvers/box-ddp.cpp:15-104) on the device: SolverDDP with the
+    box QP gains of SolverBoxFDDP on knots whose model has control limits, whether or not
+    the candidate is feasible, and clamped controls in the rollout. th_stop defaults to
+    5e-5. Needs device models."""
+
+    _kind = _abi.SOLVER_BOXDDP
+
+    def __init__(self, problem):
+        super().__init__(problem)
+        self._prm.th_stop = 5e-5
+        self._push_params()
+
+    Quu_inv = SolverBoxFDDP.Quu_inv

@@ -557,6 +557,31 @@ class SolverBoxFDDP : public SolverFDDP {
   }
 };
 
+// SolverDDP (ddp.hpp:46-306, ddp.cpp:39-310) on the GPU: the handle's solver kind
+// FDDP_SOLVER_DDP (fddp_hip.h). It shares SolverFDDP's methods by inheritance (the reference
+// derives the other way round): forwardPass / tryStep are SolverDDP's rollout,
+// expectedImprovement / get_d its d without gap terms, solve its acceptance rule.
+class SolverDDP : public SolverFDDP {
+ public:
+  explicit SolverDDP(std::shared_ptr<ShootingProblem> problem, int device = 0) : SolverDDP(problem, device, FDDP_SOLVER_DDP) {}
+
+ protected:
+  SolverDDP(std::shared_ptr<ShootingProblem> problem, int device, int kind) : SolverFDDP(problem, device) {
+    check(fddp_set_solver_kind(h_.get(), kind), "fddp_set_solver_kind");
+  }
+};
+
+// SolverBoxDDP (box-ddp.cpp:15-104): SolverDDP with the box-QP gains on limited knots whether
+// or not the candidate is feasible, clamped controls in the rollout; th_stop = 5e-5 (:25).
+class SolverBoxDDP : public SolverDDP {
+ public:
+  explicit SolverBoxDDP(std::shared_ptr<ShootingProblem> problem, int device = 0)
+      : SolverDDP(problem, device, FDDP_SOLVER_BOXDDP) {
+    params_.th_stop = 5e-5;
+    push();
+  }
+};
+
 }  // namespace crocoddyl_amd
 
 #endif  // CROCODDYL_AMD_SOLVER_FDDP_HIP_HPP_

@@ -438,9 +438,24 @@ int fddp_set_debug(fddp_handle* h, int on);
  * ABI leaves th_stop to fddp_set_params (the facades apply the default). */
 #define FDDP_SOLVER_FDDP 0
 #define FDDP_SOLVER_BOXFDDP 1
-/* Replaces constructing SolverBoxFDDP(problem) instead of SolverFDDP(problem)
- * (box-fddp.cpp:15-29). FDDP_ERR_UNSUPPORTED if BOXFDDP is asked with
- * nu_max > 64 (one wave holds one box QP). */
+/* DDP: SolverDDP (ddp.cpp:39-310). The same calcDiff and backward pass (gap terms
+ * Vx += Vxx fs on an infeasible candidate); forwardPass closes no gap at any step
+ * length (SolverFDDP's rollout of a feasible candidate); expectedImprovement is
+ * d = (sum Qu.k, -sum k.Quu k), without gap terms and independent of the trial;
+ * a step is accepted only if dVexp >= 0 and (d[0] < th_grad, or the candidate is
+ * infeasible, or dV > th_acceptstep * dVexp); th_acceptnegstep is unused; the
+ * iterate is feasible after any accepted step. fddp_solve, fddp_forward_pass,
+ * fddp_try_step, fddp_expected_improvement and fddp_result follow these rules;
+ * everything else keeps its meaning.
+ * BOXDDP: SolverBoxDDP (box-ddp.cpp:15-104): DDP with SolverBoxFDDP's box QP
+ * gains on limited knots whether or not the candidate is feasible, and us_try
+ * clamped to the limits. As for BOXFDDP, the facades set th_stop = 5e-5. */
+#define FDDP_SOLVER_DDP 2
+#define FDDP_SOLVER_BOXDDP 3
+/* Replaces constructing SolverBoxFDDP / SolverDDP / SolverBoxDDP(problem) instead
+ * of SolverFDDP(problem) (box-fddp.cpp:15-29). Trajectories, gains and limits of
+ * a live handle are kept across a switch. FDDP_ERR_UNSUPPORTED if BOXFDDP or
+ * BOXDDP is asked with nu_max > 64 (one wave holds one box QP). */
 int fddp_set_solver_kind(fddp_handle* h, int kind);
 int fddp_get_solver_kind(fddp_handle* h, int* kind);
 /* Control limits of every running knot and element: u_lb, u_ub are
