@@ -122,6 +122,7 @@ PROTOS_GPU = {
     "get_params": (C.c_int, [P, C.POINTER(Params)]),
     "get_xs": (C.c_int, [P, D, C.c_int]),
     "get_us": (C.c_int, [P, D, C.c_int]),
+    "quasi_static": (C.c_int, [P, D, D, C.c_int]),
     "get_xs_try": (C.c_int, [P, D]),
     "get_us_try": (C.c_int, [P, D]),
     "set_debug": (C.c_int, [P, C.c_int]),

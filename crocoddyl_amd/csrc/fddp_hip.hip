@@ -201,6 +201,7 @@ struct fddp_handle_s {
   double* staging = nullptr;
   int64_t staging_len = 0;
   double* d_out = nullptr;  // B doubles
+  double* qs_out = nullptr;  // fddp_quasi_static with host pointers: B x T x nu_max, allocated on first use
   int* d_count = nullptr;
   int* h_count = nullptr;   // pinned
   bool debug = false;
@@ -1203,6 +1204,44 @@ int fddp_get_us(fddp_handle* h, double* out, int on_device) {
   DeviceGuard g(h->device);
   if (h->D.m == 0) return FDDP_OK;
   return gather_traj(h, 1, 0, out, on_device);
+}
+int fddp_quasi_static(fddp_handle* h, const double* xs, double* us, int on_device) {
+  if (!h || !us) return fail(FDDP_ERR_INVALID_ARG, "fddp_quasi_static: null");
+  DeviceGuard g(h->device);
+  const Dev& D = h->D;
+  // (the reference's generic Newton quasiStatic, action-base.hxx:40-69, is not covered)
+  for (int t = 0; t < D.T; ++t)
+    if (h->knots[t].nu > 0 && !is_mb_kind(h->knots[t].kind))
+      return fail(FDDP_ERR_UNSUPPORTED, "fddp_quasi_static: knot " + std::to_string(t) +
+                                            " is not a multibody knot (quasiStatic is covered for the multibody models)");
+  if (h->plan.lds.qs_error) return fail(FDDP_ERR_UNSUPPORTED, std::string("fddp_quasi_static: ") + h->plan.lds.qs_error);
+  if (D.T == 0 || D.m == 0) return FDDP_OK;
+  const int64_t lx = (int64_t)D.B * (D.T + 1) * D.nx, lu = (int64_t)D.B * D.T * D.m;
+  const double* dxs = xs;
+  double* dus = us;
+  if (!on_device) {
+    int rc;
+    if (!h->qs_out && (rc = dalloc(h, &h->qs_out, lu))) return rc;
+    if (xs) {
+      HIP_TRY(hipMemcpyAsync(h->staging, xs, sizeof(double) * lx, hipMemcpyHostToDevice, h->stream));
+      dxs = h->staging;
+    }
+    dus = h->qs_out;
+  }
+  if (h->plan.lds.qs_smem == 0) {  // no running knot has controls to find: zero rows
+    HIP_TRY(hipMemsetAsync(dus, 0, sizeof(double) * lu, h->stream));
+  } else {
+    // (the attribute is per kernel, not per handle: asked for at every call, so that another handle's smaller
+    // plan in between does not leave this launch short)
+    HIP_TRY(hipFuncSetAttribute(ktab::quasi_static_fn(), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)h->plan.lds.qs_smem));
+    KLAUNCH(ktab::quasi_static(dim3(D.T, D.B), h->plan.lds.qs_smem, h->stream, D, dxs, dus, h->plan.lds.qsw));
+  }
+  if (!on_device) {
+    HIP_TRY(hipMemcpyAsync(us, h->qs_out, sizeof(double) * lu, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  return FDDP_OK;
 }
 int fddp_get_xs_try(fddp_handle* h, double* out) {
   if (!h || !out) return fail(FDDP_ERR_INVALID_ARG, "fddp_get_xs_try: null");

@@ -51,6 +51,11 @@ hipError_t calc_diff(dim3 grid, size_t smem, hipStream_t s, const Dev& D, int se
 hipError_t calc_tiled(dim3 grid, size_t smem, hipStream_t s, const Dev& D, int sel_calc, int sel_diff, int gaps,
                       int64_t pcap);
 
+// Quasi-static controls of the multibody running knots (k_qs.hip): grid (T, B), 256 threads;
+// wd: the work area's doubles (LdsPlan::qsw), smem: LdsPlan::qs_smem
+const void* quasi_static_fn();
+hipError_t quasi_static(dim3 grid, size_t smem, hipStream_t s, const Dev& D, const double* xs, double* us, int64_t wd);
+
 }  // namespace ktab
 }  // namespace fddp
 

@@ -20,6 +20,7 @@
 #include "fast_path.hpp"
 #include "ktab.hpp"
 #include "multibody.hpp"
+#include "mb_quasistatic.hpp"
 
 namespace fddp {
 namespace plan {
@@ -68,6 +69,9 @@ struct LdsPlan {
   int mbspill = 0, dxv_mbw = 0;           // Dev::mbspill, dxv_mbw
   int64_t mb_all_lds = 0;       // bytes of the calcDiff's all-LDS plan (what the spill rule weighs)
   size_t mb_diff_smem = 0;      // dynamic LDS of mb_knot_kernel under the plan's flags
+  int64_t qsw = 0;              // LDS doubles of the quasi-static knot's work area (0: no running multibody knot with controls)
+  size_t qs_smem = 0;           // dynamic LDS of quasi_static_kernel: the work area, the state, the parameter block
+  const char* qs_error = nullptr;  // why fddp_quasi_static is refused on these knots (the handle itself stands)
   int64_t pcap = 0;             // doubles of LDS reserved for a resident parameter block
   size_t fwd_smem = 0, calc_smem = 0, cdiff_smem = 0, fused_smem = 0, fwd_fast_smem = 0;
   bool fast = false;            // dense-knot fast path (fast_path.hpp) for calc / calcDiff / forward
@@ -393,6 +397,8 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
         mb_act = mb_act || k.act;
         mb_nu = std::max(mb_nu, k.nu);
         mb_nrows = std::max(mb_nrows, k.nrows);
+        if (s1 >= 0 && t < d.T && knots[t].kind != FDDP_KNOT_IMPULSEFWD && k.nu > 0)
+          p.qsw = std::max<int64_t>(p.qsw, pad2(fddp::mb::quasi_static_work_doubles(k.nj, k.nc, k.nu)));
         bool seen = false;
         for (const MbShape& q : shapes)
           seen = seen || (q.nj == k.nj && q.njac == k.njac && q.nc == k.nc && q.nu == k.nu && q.nrows == k.nrows &&
@@ -434,6 +440,8 @@ inline LdsPlan plan_lds(const fddp_dims& d, const fddp_knot_desc* knots, const d
                   : 0;
   p.mbd = p.has_mb ? plan_doubles(p.mbspill) : 0;
   p.mb_diff_smem = p.has_mb ? sizeof(double) * (p.mbd + pad2(mb_pmax)) : 0;
+  p.qs_smem = p.qsw ? sizeof(double) * (p.qsw + pad2(d.nx) + pad2(mb_pmax)) : 0;
+  if (p.qs_smem > 160 * 1024) p.qs_error = "the quasi-static knot's work area and parameter block exceed the CU's LDS";
   const int64_t budget = (150 * 1024) / 8 - (2 * sX + sM + 2 * sN + 5 * (kNT / kWave) + 16) - p.mbw;
   // LDS-staged parameter blocks up to pcap doubles; larger (dense) blocks are read from
   // global memory. The multibody calc reads its block from LDS only (knots.hpp), so

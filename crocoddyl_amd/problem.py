@@ -427,6 +427,40 @@ class ShootingProblem:
     def rollout_us(self, us):
         return self.rollout(us)
 
+    def quasiStatic(self, xs):
+        """shooting.hxx quasiStatic: us[t] = runningModels[t].quasiStatic(xs[t]), the controls that
+        hold (q, 0) still, for every running knot and batch element in one device call
+        (fddp_quasi_static). xs as for calc, with T or T + 1 states (the terminal one is not read);
+        the result has rollout's form for controls (a knot without controls: an empty / zero row)."""
+        unsupported = "crocoddyl_amd: quasiStatic is covered for the multibody models"
+        if self.host_mode:
+            xs = list(xs)
+            if len(xs) not in (self.T, self.T + 1):
+                raise ValueError(f"Invalid argument: xs has wrong dimension (it should be {self.T + 1})")
+            us = []
+            for m, d, x in zip(self._models, self.runningDatas, xs):
+                if m.nu == 0:
+                    us.append(np.zeros(0))
+                elif not hasattr(m, "quasiStatic"):
+                    raise NotImplementedError(unsupported)
+                else:
+                    us.append(np.asarray(m.quasiStatic(d, np.asarray(x, float)), float))
+            return us
+        for m in self._models:
+            if m.nu > 0 and not getattr(m, "_mb", False):
+                raise NotImplementedError(unsupported)
+        if isinstance(xs, (list, tuple)) and len(xs) == self.T:
+            xs = list(xs) + [xs[-1]]
+        elif not isinstance(xs, (list, tuple)) and np.ndim(xs) >= 2 and np.shape(xs)[-2] == self.T:
+            xs = np.concatenate([np.asarray(xs, float), np.asarray(xs, float)[..., -1:, :]], axis=-2)
+        xa = self._xs_array(xs)
+        if xa is None:
+            raise ValueError(f"Invalid argument: xs has wrong dimension (it should be {self.T + 1})")
+        h = self._calc_handle()
+        us = np.zeros((self.B, self.T, self.nu_max))
+        check(lib().fddp_quasi_static(h, _abi.dptr(xa), _abi.dptr(us), 0))
+        return self._out_u(us)
+
 
 def _cm(flat, r, c):
     """(B, r*c) column-major rows -> (B, r, c)."""

@@ -192,6 +192,7 @@ class ShootingProblem {
   int get_nu_max() const { return nu_max_; }
   int get_B() const { return B_; }
   const VectorXd& get_x0() const { return x0_; }
+  const std::vector<std::shared_ptr<ActionModelBase> >& get_runningModels() const { return running_; }
   template <class V>
   void set_x0(const V& x0) {  // shooting.hxx:391-397
     VectorXd v = to_vec(x0);
@@ -429,6 +430,33 @@ class SolverFDDP {
     check(fddp_set_candidate(h_.get(), xs.empty() ? nullptr : xs.data(), us.empty() ? nullptr : us.data(),
                              is_feasible ? 1 : 0),
           "fddp_set_candidate");
+  }
+
+  // ShootingProblem::quasiStatic (shooting.hxx) on the device: us[t] = the controls that hold
+  // xs[t] = (q, 0) still on running knot t (fddp_quasi_static; multibody knots, else the library
+  // refuses). xs: T or T + 1 states (the terminal one is not read), shared by the batch. B = 1:
+  // every vector cut to its knot's nu (a knot without controls: empty), ready for solve();
+  // batched: element 0's rows at nu_max, as get_us(). The candidate and the solver state are
+  // left alone. (The C++ ShootingProblem owns no device handle, hence a solver method.)
+  template <class V>
+  std::vector<VectorXd> quasiStatic(const std::vector<V>& xs) const {
+    const int T = dims_.T, nx = dims_.nx, nu = dims_.nu_max, B = dims_.B;
+    if ((int)xs.size() != T && (int)xs.size() != T + 1) throw Exception("Invalid argument: xs has wrong dimension");
+    VectorXd flat;
+    for (int b = 0; b < B; ++b)
+      for (int t = 0; t <= T; ++t) {
+        const V& x = xs[t < (int)xs.size() ? t : T - 1];
+        if ((int)x.size() != nx) throw Exception("Invalid argument: xs has wrong dimension");
+        flat.insert(flat.end(), x.data(), x.data() + nx);
+      }
+    VectorXd a((size_t)B * T * nu + 1, 0.);
+    check(fddp_quasi_static(h_.get(), flat.data(), a.data(), 0), "fddp_quasi_static");
+    std::vector<VectorXd> out;
+    for (int t = 0; t < T; ++t) {
+      const int n = B == 1 ? problem_->get_runningModels()[t]->nu() : nu;
+      out.push_back(VectorXd(a.begin() + (size_t)t * nu, a.begin() + (size_t)t * nu + n));
+    }
+    return out;
   }
 
   std::vector<VectorXd> get_xs() const {  // element 0 (B = 1: the problem)

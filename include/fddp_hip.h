@@ -337,6 +337,16 @@ int fddp_get_results(fddp_handle* h, fddp_result* out);
  * on the handle's device (copy is enqueued on the handle's stream). */
 int fddp_get_xs(fddp_handle* h, double* out, int on_device);
 int fddp_get_us(fddp_handle* h, double* out, int on_device);
+/* us[b][t] = quasiStatic(model_t, xs[b][t]) for every running knot: B x T x nu_max out,
+ * xs B x (T+1) x nx in (the terminal row is not read); xs == NULL: the handle's current
+ * candidate states. on_device: both pointers are device pointers (as fddp_get_xs). The u that
+ * holds x = (q, 0) still (the velocity part of x is ignored): u = (pinv([dtau/du(0) | Jc^T])
+ * g(q))[0:nu], the minimum-norm least-squares solution with the singular values at or below
+ * max(nv, nu + nc) eps sigma_max truncated. A knot's entries beyond its nu, and an impulse knot's
+ * row, are zero; a non-finite q gives that knot a NaN row. Runs on the handle's stream and leaves
+ * the candidate, the solver state and the datas alone. FDDP_ERR_UNSUPPORTED (naming the knot) if a
+ * running knot with nu > 0 is not a multibody knot. */
+int fddp_quasi_static(fddp_handle* h, const double* xs, double* us, int on_device);
 
 /* ---- step API: the SolverDDP/SolverFDDP methods one at a time --------------
  * Used for parity tests against the reference's own step-level tests
