@@ -256,4 +256,22 @@ __device__ __forceinline__ bool box_qp_wave(const double* H, int ldh, double* Qi
   return true;
 }
 
+// What box_qp_wave (remap = true) left in Qi, formed again from the two free sets it returned:
+// the same inv on the same matrix, so the same bits. free_sol == free_inv: the embedded Hff_inv of
+// that set (a QP converged at its first iteration, or on the free set of its last Newton step, or
+// stopped at maxiter / a fixed point); an empty free_sol: zeros; else the remapped inverse. True on
+// a failed pivot (none, where the QP's own inverse had none).
+template <class Inv>
+__device__ __forceinline__ bool box_replay_inverse(double* Qi, int ldq, int m, int lane, uint64_t free_sol,
+                                                   uint64_t free_inv, const BoxQPCfg& c, Inv&& inv) {
+  if (c.maxiter <= 0 || (free_sol == 0 && free_inv != 0)) {
+    for (int e = lane; e < m * m; e += 64) Qi[(e / m) * ldq + e % m] = 0.;
+    asm volatile("" ::: "memory");
+    return false;
+  }
+  if (free_sol == free_inv) return inv(InvMap::plain(free_inv, m, c.reg));
+  (void)inv(InvMap::remapped(free_sol, free_inv, m, c.reg));  // (as the QP: its verdict is not read)
+  return false;
+}
+
 }  // namespace fddp

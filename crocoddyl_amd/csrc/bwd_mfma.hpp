@@ -644,12 +644,24 @@ struct BwdLds {
 // zeroed on the clamped set. Returns false where the reference raises
 // backward_error (including its qp_ size check: the QP has
 // runningModels[0]->nu variables, box-fddp.cpp:16, box-qp.cpp:53-72).
-template <int MP, int LDQ, int LDC>
+// RP (a replay of the last sweep, launch mode 2): no QP, as box_gains_generic.
+template <int MP, int LDQ, int LDC, bool RP = false>
 __device__ __forceinline__ bool box_gains_wave(const Dev& D, const BwdLds& L, int b, int t, int cur, int lane) {
   const int nu = D.knots[t].nu;
   if (nu != D.knots[0].nu) return false;
   const int64_t rr = D.run(b, t);
   const bool valid = lane < nu;
+  if constexpr (RP) {
+    const uint64_t fsol = D.bmask[2 * rr], finv = D.bmask[2 * rr + 1];
+    auto inv = [&](const InvMap& mp) { return sym_sweep_inverse_masked<MP, LDQ, LDC>(L.Quu, L.Qi, L.rowbuf, nu, lane, mp); };
+    if (box_replay_inverse(L.Qi, LDC, nu, lane, fsol, finv, D.boxcfg, inv)) return false;
+    asm volatile("" ::: "memory");
+    if (lane < MP) L.kv[lane] = valid ? D.k[rr * D.sM + lane] : 0.;
+    if (valid && !((fsol >> lane) & 1)) L.qu[lane] = 0.;
+    if (D.dQuuInv)
+      for (int e = lane; e < nu * nu; e += 64) D.dQuuInv[rr * D.sMM + (e / nu) * D.m + e % nu] = L.Qi[(e / nu) * LDC + e % nu];
+    return true;
+  }
   double q = 0., lb = 0., ub = 0., x = 0.;
   if (valid) {
     const double u = D.us[cur][rr * D.sM + lane];
@@ -673,6 +685,12 @@ __device__ __forceinline__ bool box_gains_wave(const Dev& D, const BwdLds& L, in
     atomicAdd(D.box_stats + 2, (unsigned long long)ninv);
   }
   if (!qp_ok) return false;
+  // for a replay of this sweep (D.bmask is allocated with D.haslim, without which no knot comes
+  // here; no test of the pointer: with one, backward_mfma_ddp_kernel<5, 2, 8> spilled 70 VGPRs for 64)
+  if (lane == 0) {
+    D.bmask[2 * rr] = fsol;
+    D.bmask[2 * rr + 1] = finv;
+  }
   asm volatile("" ::: "memory");
   if (lane < MP) L.kv[lane] = valid ? -x : 0.;
   if (valid) {
@@ -686,7 +704,7 @@ __device__ __forceinline__ bool box_gains_wave(const Dev& D, const BwdLds& L, in
 
 // One knot of the sweep, as executed by wave W (all four waves call this
 // with their own W; the barriers inside line up one to one).
-template <int NTL, int MTL, int NW, int W>
+template <int NTL, int MTL, int NW, int W, bool RP = false>
 __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, int t, bool feas, bool boxqp, double xreg,
                                          double ureg, int cur, Stamp& stamp, double (&red5)[5]) {
   using Cfg = MfmaCfg<NTL, MTL>;
@@ -967,7 +985,7 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
       lds_wait_ge(L.flag + 1, target);
     }
     if (boxk) {
-      if (!box_gains_wave<MP, LDQ, LDC>(D, L, b, t, cur, lane) && lane == 0) *L.flag = 1;
+      if (!box_gains_wave<MP, LDQ, LDC, RP>(D, L, b, t, cur, lane) && lane == 0) *L.flag = 1;
     } else {
       // C = Lc^-1 into Qi (the gains as K = C^T (C Qxu^T), k = C^T (C Qu)), and C^T where
       // it has an area of its own
@@ -1262,7 +1280,7 @@ __device__ __forceinline__ bool bwd_knot(const Dev& D, const BwdLds& L, int b, i
   return true;
 }
 
-template <int NTL, int MTL, int NW>
+template <int NTL, int MTL, int NW, bool RP = false>
 __device__ __forceinline__ bool bwd_sweep_mfma(const Dev& D, int b, bool feas, bool boxqp, double xreg, double ureg,
                                                int cur, double* sm, double (&ei)[3], bool ddp) {
   double red5[5] = {0., 0., 0., 0., 0.};  // running sums (C^T in its own area: the small shapes)
@@ -1389,14 +1407,14 @@ __device__ __forceinline__ bool bwd_sweep_mfma(const Dev& D, int b, bool feas, b
     stamp.mark(7);
     bool ok = false;
     switch (wid) {
-      case 0: ok = bwd_knot<NTL, MTL, NW, 0>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
-      case 1: ok = bwd_knot<NTL, MTL, NW, 1>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
-      case 2: ok = bwd_knot<NTL, MTL, NW, 2>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
-      case 3: ok = bwd_knot<NTL, MTL, NW, 3>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
-      case 4: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 4>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
-      case 5: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 5>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
-      case 6: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 6>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
-      default: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 7>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 0: ok = bwd_knot<NTL, MTL, NW, 0, RP>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 1: ok = bwd_knot<NTL, MTL, NW, 1, RP>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 2: ok = bwd_knot<NTL, MTL, NW, 2, RP>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 3: ok = bwd_knot<NTL, MTL, NW, 3, RP>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 4: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 4, RP>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 5: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 5, RP>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      case 6: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 6, RP>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
+      default: if constexpr (NW > 4) ok = bwd_knot<NTL, MTL, NW, 7, RP>(D, L, b, t, feas, boxqp, xreg, ureg, cur, stamp, red5); break;
     }
     if (!ok) {  // the factorisation failed (every wave saw the flag)
       stamp.flush();
@@ -1491,6 +1509,12 @@ constexpr size_t bwd_lds_bytes() {
     st->xreg = xreg;                                                                         \
     st->ureg = ureg;                                                                         \
     st->bwd_fail = ok ? 0 : 1;                                                               \
+    /* what this sweep's last attempt ran with, for a replay (backward_mfma_replay_kernel) */ \
+    SweepRec* const rec = D.rec + b;                                                         \
+    rec->xreg = xreg;                                                                        \
+    rec->ureg = ureg;                                                                        \
+    rec->feas = feas ? 1 : 0;                                                                \
+    rec->cur = st->cur;                                                                      \
     if (!ok && mode == 0) {                                                                  \
       st->status = FDDP_STATUS_REGMAX;                                                       \
       st->active = 0;                                                                        \
@@ -1542,6 +1566,22 @@ template <int NTL, int MTL, int NW>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4 ? 2 : 1))) void backward_mfma_ddp_kernel(
     Dev D, Prm prm, int mode) {
   FDDP_BACKWARD_MFMA_BODY(true)
+}
+
+
+// Launch mode 2, the replay (backward_replay_kernel in fddp_kernels.hpp): every element's last
+// sweep once more with what SweepRec says it ran with, one attempt, for the d* stores it fills.
+// Built with the DDP solver kinds for every plan; ElemState is not touched.
+template <int NTL, int MTL, int NW>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4 ? 2 : 1))) void backward_mfma_replay_kernel(
+    Dev D, int ddp) {
+  const int b = blockIdx.x;
+  const SweepRec rec = D.rec[b];
+  if (rec.cur < 0) return;  // never swept: its stores stay zero
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const bool feas = rec.feas != 0;
+  double ei[3];
+  (void)bwd_sweep_mfma<NTL, MTL, NW, true>(D, b, feas, feas || D.box > 1, rec.xreg, rec.ureg, rec.cur, sm, ei, ddp != 0);
 }
 
 }  // namespace fddp

@@ -40,6 +40,15 @@ struct ElemState {
 
 static_assert(sizeof(ElemState) % 8 == 0, "ElemState alignment");
 
+// What an element's last backward sweep ran with (its last attempt, after any regularisation
+// retries), written by thread 0 at the end of the sweep kernels: the forward pass changes all four
+// in ElemState when it accepts a step, and a replay of the sweep (launch mode 2, which fills the
+// SolverDDP getters' stores: sweep_stores.hpp) needs the sweep's own. cur < 0: never swept.
+struct SweepRec {
+  double xreg, ureg;
+  int32_t feas, cur;
+};
+
 
 __host__ __device__ inline int64_t pad2(int64_t v) { return (v + 1) & ~int64_t(1); }
 
@@ -231,6 +240,10 @@ struct Dev {
   double *pxs, *pus, *pxnext, *pkcost, *pdvp;  // slots 1..npar-1: [slot][B][T+1|T][...]
   double* ptrial;                  // [B][npar][4]: ok, cost_try, dv, -
   int* ls_done;                    // [B] line search decided in an earlier group of this iteration
+  // replay of the last sweep (sweep_stores.hpp). Last in the struct: the members above keep
+  // their kernel-argument offsets.
+  SweepRec* rec;                   // [B] what each element's last sweep ran with
+  unsigned long long* bmask;       // [B][T][2] free sets (solution, inverse) of each knot's last box QP (null = no limits set)
   // The accessors are always inlined: a kernel that calls one out of line passes the address of
   // its by-value Dev argument, and the whole struct then lives in scratch memory (688 B per lane,
   // read back at every use; the inliner left box_knot out of the two-wave rollout whenever the

@@ -29,6 +29,7 @@
 #include "bwd_mfma.hpp"
 #include "ktab.hpp"
 #include "launch_plan.hpp"
+#include "sweep_stores.hpp"
 
 using namespace fddp;
 using plan::block_doubles;
@@ -75,6 +76,9 @@ int backward_mfma_setup(int ntl, int mtl, int nw, int n, int* per_cu) {
 }
 hipError_t backward_mfma(int code, dim3 grid, hipStream_t s, const Dev& D, const Prm& prm, int mode) {
   return code == 528 ? backward_mfma_0(code, grid, s, D, prm, mode) : backward_mfma_1(code, grid, s, D, prm, mode);
+}
+hipError_t backward_mfma_replay(int code, dim3 grid, hipStream_t s, const Dev& D, int ddp) {
+  return code == 528 ? backward_mfma_replay_3(grid, s, D, ddp) : backward_mfma_replay_1(code, grid, s, D, ddp);
 }
 }  // namespace ktab
 }  // namespace fddp
@@ -206,7 +210,8 @@ struct fddp_handle_s {
   int* h_count = nullptr;   // pinned
   bool debug = false;
   double* dbg[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  double* dqi = nullptr;  // SolverBoxFDDP::Quu_inv_ debug store (allocated with debug on)
+  double* dqi = nullptr;  // SolverBoxFDDP::Quu_inv_ store (allocated with the seven above)
+  stores::SweepStores ss;  // whether those stores hold the last sweep's values, or a replay can fill them
   int solver_kind = FDDP_SOLVER_FDDP;
   double* d_ulb = nullptr;  // control limits, allocated on first fddp_set_control_limits
   double* d_uub = nullptr;
@@ -317,6 +322,7 @@ BoxQPCfg to_boxcfg(const fddp_boxqp_params& p) {
 // ---- kernel launchers ------------------------------------------------------
 int launch_fused(fddp_handle* h, int sel_calc, int sel_diff, int gaps) {
   Timed tm(h, sel_diff >= 0 ? 1 : 0);
+  if (sel_diff >= 0) h->ss.on_inputs_written();  // a calcDiff: the derivative blocks and fs
   const Dev& D = h->D;
   KLAUNCH(ktab::calc_tiled(dim3(D.B), h->plan.lds.fused_smem, h->stream, D, sel_calc, sel_diff, gaps, h->plan.lds.pcap));
   return FDDP_OK;
@@ -324,6 +330,7 @@ int launch_fused(fddp_handle* h, int sel_calc, int sel_diff, int gaps) {
 // Multibody knots (knot-parallel): calc for sel_calc, calcDiff for sel_diff (-1: none).
 int launch_mb(fddp_handle* h, int sel_calc, int sel_diff) {
   const Dev& D = h->D;
+  if (sel_diff >= 0) h->ss.on_inputs_written();
   KLAUNCH(ktab::mb_knot(h->plan.var.mb, dim3(D.T + 1, D.B), h->plan.lds.mb_diff_smem, h->stream, D, sel_calc, sel_diff));
   return FDDP_OK;
 }
@@ -351,6 +358,7 @@ int launch_cost_sum(fddp_handle* h, int sel, double* out) {
 // no calcDiff work: the gaps alone, one wave per (knot, element).
 int launch_dense_diff_gaps(fddp_handle* h, int sel, int gaps) {
   const Dev& D = h->D;
+  h->ss.on_inputs_written();
   if (!h->plan.lds.all_mb) {
     KLAUNCH(ktab::calc_diff(dim3(D.B), h->plan.lds.cdiff_smem, h->stream, D, sel, gaps, h->plan.lds.pcap));
   } else if (gaps) {
@@ -393,10 +401,52 @@ int launch_calc_then_diff(fddp_handle* h, int sel_calc, int sel_calc_sum, int se
 int launch_backward(fddp_handle* h, int mode) {
   Timed tm(h, 2);
   const Dev& D = h->D;
+  h->ss.on_sweep(h->debug);
   if (h->plan.var.bwd)
     KLAUNCH(ktab::backward_mfma(h->plan.var.bwd, dim3(D.B), h->stream, D, to_prm(h), mode));
   else
     KLAUNCH(ktab::backward_generic(dim3(D.B), h->bwd_smem, h->stream, D, to_prm(h), mode));
+  return FDDP_OK;
+}
+// The SolverDDP getters' stores, zero-filled, allocated once: by fddp_set_debug(h, 1) or by the
+// first read that replays (they stay until fddp_destroy).
+int ensure_stores(fddp_handle* h) {
+  const Dev& D = h->D;
+  int rc;
+  if (!h->dbg[0]) {
+    const int64_t B = D.B, K1 = D.T + 1, K0 = D.T;
+    const int64_t sizes[7] = {B * K1 * D.sNN, B * K1 * D.sN, B * K0 * D.sNN, B * K0 * D.sNM,
+                              B * K0 * D.sMM, B * K0 * D.sN, B * K0 * D.sM};
+    for (int i = 0; i < 7; ++i)
+      if ((rc = dalloc(h, &h->dbg[i], sizes[i]))) return rc;
+  }
+  if (!h->dqi && (rc = dalloc(h, &h->dqi, (int64_t)D.B * D.T * D.sMM))) return rc;
+  return FDDP_OK;
+}
+void set_store_pointers(fddp_handle* h, Dev& D, bool on) {
+  double* const* p = h->dbg;
+  D.dVxx = on ? p[0] : nullptr;
+  D.dVx = on ? p[1] : nullptr;
+  D.dQxx = on ? p[2] : nullptr;
+  D.dQxu = on ? p[3] : nullptr;
+  D.dQuu = on ? p[4] : nullptr;
+  D.dQx = on ? p[5] : nullptr;
+  D.dQu = on ? p[6] : nullptr;
+  D.dQuuInv = on ? h->dqi : nullptr;
+}
+// Launch mode 2: every element's last sweep once more, by the plan that ran it, with the stores'
+// pointers in its Dev (sweep_stores.hpp). Counted as a backward launch by the timers.
+int launch_replay(fddp_handle* h) {
+  int rc;
+  if ((rc = ensure_stores(h))) return rc;
+  Timed tm(h, 2);
+  Dev D = h->D;
+  set_store_pointers(h, D, true);
+  if (h->plan.var.bwd)
+    KLAUNCH(ktab::backward_mfma_replay(h->plan.var.bwd, dim3(D.B), h->stream, D, ddp_kind(h->solver_kind) ? 1 : 0));
+  else
+    KLAUNCH(ktab::backward_generic_replay(dim3(D.B), h->bwd_smem, h->stream, D));
+  h->ss.on_replay();
   return FDDP_OK;
 }
 
@@ -844,6 +894,11 @@ int fddp_create(const fddp_dims* dims, const fddp_knot_desc* knots, const double
   double* stp = nullptr;
   if ((rc = dalloc(h, &stp, (int64_t)(sizeof(ElemState) / 8) * B))) return bail(rc);
   D.st = (ElemState*)stp;
+  double* recp = nullptr;  // cur = -1 everywhere: no element has swept
+  if ((rc = dalloc(h, &recp, (int64_t)(sizeof(SweepRec) / 8) * B))) return bail(rc);
+  D.rec = (SweepRec*)recp;
+  if (hipMemsetAsync(recp, 0xff, sizeof(SweepRec) * B, h->stream) != hipSuccess)
+    return bail(fail(FDDP_ERR_RUNTIME, "init sweep records"));
   h->staging_len = std::max<int64_t>(std::max<int64_t>(B * K1 * d.nx, B * K0 * D.sM), B * K1);
   if ((rc = dalloc(h, &h->staging, h->staging_len))) return bail(rc);
   if ((rc = dalloc(h, &h->d_out, 2 * B))) return bail(rc);
@@ -1395,29 +1450,10 @@ int fddp_set_solver_state(fddp_handle* h, int iter, double xreg, double ureg, in
 int fddp_set_debug(fddp_handle* h, int on) {
   if (!h) return fail(FDDP_ERR_INVALID_ARG, "null handle");
   DeviceGuard g(h->device);
-  Dev& D = h->D;
-  if (on && !h->dbg[0]) {
-    const int64_t B = D.B, K1 = D.T + 1, K0 = D.T;
-    const int64_t sizes[7] = {B * K1 * D.sNN, B * K1 * D.sN, B * K0 * D.sNN, B * K0 * D.sNM,
-                              B * K0 * D.sMM, B * K0 * D.sN, B * K0 * D.sM};
-    int rc;
-    for (int i = 0; i < 7; ++i)
-      if ((rc = dalloc(h, &h->dbg[i], sizes[i]))) return rc;
-  }
-  double* const* p = h->dbg;
   const bool a = on != 0;
-  D.dVxx = a ? p[0] : nullptr;
-  D.dVx = a ? p[1] : nullptr;
-  D.dQxx = a ? p[2] : nullptr;
-  D.dQxu = a ? p[3] : nullptr;
-  D.dQuu = a ? p[4] : nullptr;
-  D.dQx = a ? p[5] : nullptr;
-  D.dQu = a ? p[6] : nullptr;
-  if (on && !h->dqi) {
-    int rc;
-    if ((rc = dalloc(h, &h->dqi, (int64_t)D.B * D.T * D.sMM))) return rc;
-  }
-  D.dQuuInv = a ? h->dqi : nullptr;
+  int rc;
+  if (a && (rc = ensure_stores(h))) return rc;
+  set_store_pointers(h, h->D, a);
   h->debug = a;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return FDDP_OK;
@@ -1431,6 +1467,22 @@ int fddp_get_quantity(fddp_handle* h, int which, double* out) {
   const double* src = nullptr;
   int64_t per = 0, stride = 0, nk = 0;
   int cur = -1;
+  if (which >= FDDP_Q_VXX && which <= FDDP_Q_QUU_INV) {
+    // the SolverDDP getters (sweep_stores.hpp): debug mode as it always was; else the stores if
+    // they hold the last sweep's values, a replay of that sweep into them, zeros before any sweep
+    int rc;
+    switch (h->ss.on_read(h->debug)) {
+      case stores::READ_COPY: break;
+      case stores::READ_REPLAY:
+        if ((rc = launch_replay(h))) return rc;
+        break;
+      case stores::READ_ZEROS:
+        if ((rc = ensure_stores(h))) return rc;  // (zero-filled, and nothing has written them)
+        break;
+      default: return fail(FDDP_ERR_INVALID_ARG, stores::overwritten_message());
+    }
+  }
+  const double* const* sp = h->dbg;  // (outside debug mode the handle's Dev does not carry them)
   switch (which) {
     case FDDP_Q_FX: src = D.Fx; per = n * n; stride = D.sNN; nk = D.T + 1; break;
     case FDDP_Q_FU: src = D.Fu; per = n * m; stride = D.sNM; nk = D.T + 1; break;
@@ -1444,14 +1496,14 @@ int fddp_get_quantity(fddp_handle* h, int which, double* out) {
     case FDDP_Q_FS: src = D.fs; per = n; stride = D.sN; nk = D.T + 1; break;
     case FDDP_Q_K: src = D.K; per = m * n; stride = D.sNM; nk = D.T; break;
     case FDDP_Q_KV: src = D.k; per = m; stride = D.sM; nk = D.T; break;
-    case FDDP_Q_VXX: src = D.dVxx; per = n * n; stride = D.sNN; nk = D.T + 1; break;
-    case FDDP_Q_VX: src = D.dVx; per = n; stride = D.sN; nk = D.T + 1; break;
-    case FDDP_Q_QXX: src = D.dQxx; per = n * n; stride = D.sNN; nk = D.T; break;
-    case FDDP_Q_QXU: src = D.dQxu; per = n * m; stride = D.sNM; nk = D.T; break;
-    case FDDP_Q_QUU: src = D.dQuu; per = m * m; stride = D.sMM; nk = D.T; break;
-    case FDDP_Q_QX: src = D.dQx; per = n; stride = D.sN; nk = D.T; break;
-    case FDDP_Q_QU: src = D.dQu; per = m; stride = D.sM; nk = D.T; break;
-    case FDDP_Q_QUU_INV: src = D.dQuuInv; per = m * m; stride = D.sMM; nk = D.T; break;
+    case FDDP_Q_VXX: src = sp[0]; per = n * n; stride = D.sNN; nk = D.T + 1; break;
+    case FDDP_Q_VX: src = sp[1]; per = n; stride = D.sN; nk = D.T + 1; break;
+    case FDDP_Q_QXX: src = sp[2]; per = n * n; stride = D.sNN; nk = D.T; break;
+    case FDDP_Q_QXU: src = sp[3]; per = n * m; stride = D.sNM; nk = D.T; break;
+    case FDDP_Q_QUU: src = sp[4]; per = m * m; stride = D.sMM; nk = D.T; break;
+    case FDDP_Q_QX: src = sp[5]; per = n; stride = D.sN; nk = D.T; break;
+    case FDDP_Q_QU: src = sp[6]; per = m; stride = D.sM; nk = D.T; break;
+    case FDDP_Q_QUU_INV: src = h->dqi; per = m * m; stride = D.sMM; nk = D.T; break;
     default: return fail(FDDP_ERR_INVALID_ARG, "fddp_get_quantity: unknown quantity");
   }
   if (per == 0) return FDDP_OK;
@@ -1480,6 +1532,7 @@ int fddp_set_knots(fddp_handle* h, const fddp_knot_desc* knots, const double* pa
   if ((rc = check_knots(h->dims, knots, params, n_params, "fddp_set_knots", false))) return rc;
   DeviceGuard g(h->device);
   HIP_TRY(hipStreamSynchronize(h->stream));  // no launch may still read the old knots
+  h->ss.on_inputs_written();
   return apply_knots(h, knots, params, n_params);
 }
 
@@ -1489,6 +1542,7 @@ int fddp_set_solver_kind(fddp_handle* h, int kind) {
     return fail(FDDP_ERR_INVALID_ARG, "fddp_set_solver_kind: unknown solver kind");
   if ((kind == FDDP_SOLVER_BOXFDDP || kind == FDDP_SOLVER_BOXDDP) && h->dims.nu_max > 64)
     return fail(FDDP_ERR_UNSUPPORTED, "fddp_set_solver_kind: the box QP holds at most 64 controls (one wave)");
+  if (kind != h->solver_kind) h->ss.on_inputs_written();  // the sweep's gains rule
   h->solver_kind = kind;
   h->D.box = kind == FDDP_SOLVER_BOXFDDP ? 1 : (kind == FDDP_SOLVER_BOXDDP ? 2 : 0);
   return FDDP_OK;
@@ -1506,6 +1560,7 @@ int fddp_set_control_limits(fddp_handle* h, const double* u_lb, const double* u_
     return fail(FDDP_ERR_INVALID_ARG, "fddp_set_control_limits: give both u_lb and u_ub, or neither");
   DeviceGuard g(h->device);
   Dev& D = h->D;
+  h->ss.on_inputs_written();  // which knots take the box QP
   if (!u_lb) {
     D.ulb = D.uub = nullptr;
     D.haslim = nullptr;
@@ -1519,6 +1574,8 @@ int fddp_set_control_limits(fddp_handle* h, const double* u_lb, const double* u_
     double* hl = nullptr;
     if ((rc = dalloc(h, &hl, (B * T + 7) / 8))) return rc;
     h->d_haslim = (unsigned char*)hl;
+    // the free sets of each knot's last box QP (box_gains_wave / box_gains_generic, for a replay)
+    if ((rc = dalloc(h, (double**)&D.bmask, 2 * B * T))) return rc;
   }
   // update_has_control_limits (action-base.hxx:142-144) per knot and element
   std::vector<unsigned char> lim((size_t)(B * T));
@@ -1616,6 +1673,7 @@ int fddp_mpc_shift(fddp_handle* h) {
   if (!h) return fail(FDDP_ERR_INVALID_ARG, "null handle");
   DeviceGuard g(h->device);
   const Dev& D = h->D;
+  h->ss.on_inputs_written();  // the gains move one knot down
   hipLaunchKernelGGL(mpc_shift_kernel<kNT>, dim3(D.B), dim3(kNT), 0, h->stream, D);
   LAUNCH_CHECK();
   return FDDP_OK;

@@ -418,11 +418,27 @@ struct BwdSmem {
 // sweep: the box QP (box_qp.hpp) with the LDS sweep inverse; Quu_inv into
 // Qi (ld m), k = -x into kv and D.k, Qu zeroed on the clamped set. False
 // where the reference raises backward_error.
+// RP (a replay of the last sweep, launch mode 2): no QP, which would warm-start from its own
+// solution about controls an accepted step has moved; k from D.k, and Quu_inv formed again on the
+// free sets the QP left in D.bmask (box_replay_inverse).
+template <bool RP = false>
 __device__ inline bool box_gains_generic(const Dev& D, BwdSmem& S, double* Qi, int b, int t, int cur, int lane) {
   const int nu = D.knots[t].nu, m = D.m;
   if (nu != D.knots[0].nu) return false;  // qp_ has runningModels[0]->nu variables (box-fddp.cpp:16)
   const int64_t rr = D.run(b, t);
   const bool valid = lane < nu;
+  if constexpr (RP) {
+    const uint64_t fsol = D.bmask[2 * rr], finv = D.bmask[2 * rr + 1];
+    auto inv = [&](const InvMap& mp) { return wave_sweep_inverse_lds(S.Quu, m, Qi, m, S.red, nu, mp, lane); };
+    if (box_replay_inverse(Qi, m, nu, lane, fsol, finv, D.boxcfg, inv)) return false;
+    if (valid) {
+      S.kv[lane] = D.k[rr * D.sM + lane];
+      if (!((fsol >> lane) & 1)) S.qu[lane] = 0.;
+    }
+    if (D.dQuuInv)
+      for (int e = lane; e < nu * nu; e += 64) D.dQuuInv[rr * D.sMM + (e / nu) * m + e % nu] = Qi[(e / nu) * m + e % nu];
+    return true;
+  }
   double q = 0., lb = 0., ub = 0., x = 0.;
   if (valid) {
     const double u = D.us[cur][rr * D.sM + lane];
@@ -436,6 +452,10 @@ __device__ inline bool box_gains_generic(const Dev& D, BwdSmem& S, double* Qi, i
   auto inv = [&](const InvMap& mp) { return wave_sweep_inverse_lds(S.Quu, m, Qi, m, S.red, nu, mp, lane); };
   if (!box_qp_wave(S.Quu, m, Qi, m, S.red, nu, lane, q, lb, ub, x, D.boxcfg, inv, true, fsol, finv, iters))
     return false;
+  if (lane == 0) {  // for a replay of this sweep (D.bmask is allocated with D.haslim)
+    D.bmask[2 * rr] = fsol;
+    D.bmask[2 * rr + 1] = finv;
+  }
   if (valid) {
     S.kv[lane] = -x;
     if (!((fsol >> lane) & 1)) S.qu[lane] = 0.;
@@ -445,7 +465,7 @@ __device__ inline bool box_gains_generic(const Dev& D, BwdSmem& S, double* Qi, i
   return true;
 }
 
-template <int NT>
+template <int NT, bool RP = false>
 __device__ __forceinline__ bool bwd_sweep(const Dev& D, int b, bool feas, double xreg, double ureg, int cur,
                                           BwdSmem& S) {
   const int n = D.n, m = D.m, T = D.T, tid = threadIdx.x;
@@ -533,7 +553,7 @@ __device__ __forceinline__ bool bwd_sweep(const Dev& D, int b, bool feas, double
     if (nu && (feas || D.box > 1) && D.box_knot(b, t)) {
       // box QP gains (SolverBoxDDP, D.box == 2: on an infeasible candidate too, box-ddp.cpp:44-75);
       // K = Quu_inv Qxu^T (S.A, nu x n, ld m)
-      if (tid < 64 && !box_gains_generic(D, S, S.L, b, t, cur, tid) && tid == 0) *S.flag = 1;
+      if (tid < 64 && !box_gains_generic<RP>(D, S, S.L, b, t, cur, tid) && tid == 0) *S.flag = 1;
       __syncthreads();
       if (*S.flag) return false;
       for (int e = tid; e < nu * n; e += NT) {
@@ -696,6 +716,12 @@ __global__ __launch_bounds__(NT) void backward_kernel(Dev D, Prm prm, int mode) 
     st->xreg = xreg;
     st->ureg = ureg;
     st->bwd_fail = ok ? 0 : 1;
+    // what this sweep's last attempt ran with, for a replay (backward_replay_kernel)
+    SweepRec* const rec = D.rec + b;
+    rec->xreg = xreg;
+    rec->ureg = ureg;
+    rec->feas = feas ? 1 : 0;
+    rec->cur = st->cur;
     if (!ok && mode == 0) {  // solve() returns false inside this loop body
       st->status = FDDP_STATUS_REGMAX;
       st->active = 0;
@@ -728,6 +754,22 @@ __global__ __launch_bounds__(NT) void backward_kernel(Dev D, Prm prm, int mode) 
       st->stop = stop;
     }
   }
+}
+
+// Launch mode 2, the replay: every element's last sweep once more, with what SweepRec says it ran
+// with and no retry, for the d* stores it fills (sweep_stores.hpp). ElemState is not touched; K, k,
+// Vxxfs and part are written with the values they hold (the sweep is deterministic and its inputs
+// are in place: the host launches this only while they are).
+template <int NT>
+__global__ __launch_bounds__(NT) void backward_replay_kernel(Dev D) {
+  const int b = blockIdx.x;
+  const SweepRec rec = D.rec[b];
+  if (rec.cur < 0) return;  // never swept: its stores stay zero
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  BwdSmem S(sm, D.n, D.m, D.bwork ? D.bwork + (int64_t)b * BwdSmem::work_doubles(D.n, D.m) : nullptr);
+  if (threadIdx.x == 0) *S.flag = 0;
+  __syncthreads();
+  (void)bwd_sweep<NT, true>(D, b, rec.feas != 0, rec.xreg, rec.ureg, rec.cur, S);
 }
 
 // ---------------------------------------------------------------------------

@@ -39,6 +39,9 @@ hipError_t ls_select(dim3 grid, hipStream_t s, const Dev& D, const Prm& prm, int
 // with its dynamic LDS set, or -1 if the shape does not fit (n > its padded width, LDS).
 int backward_mfma_setup(int ntl, int mtl, int nw, int n, int* per_cu = nullptr);
 hipError_t backward_mfma(int code, dim3 grid, hipStream_t s, const Dev& D, const Prm& prm, int mode);
+// launch mode 2: the replay of every element's last sweep (sweep_stores.hpp), by the same plan
+hipError_t backward_mfma_replay(int code, dim3 grid, hipStream_t s, const Dev& D, int ddp);
+hipError_t backward_generic_replay(dim3 grid, size_t smem, hipStream_t s, const Dev& D);
 const void* backward_generic_fn();
 hipError_t backward_generic(dim3 grid, size_t smem, hipStream_t s, const Dev& D, const Prm& prm, int mode);
 
@@ -95,6 +98,8 @@ hipError_t backward_mfma_1(int code, dim3 grid, hipStream_t s, const Dev& D, con
 // the 5 x 2 x 8 plan's kernel with the DDP solver kinds (SolverDDP / SolverBoxDDP handles)
 hipError_t backward_mfma_ddp_setup_2(int lds);
 void backward_mfma_ddp_2(dim3 grid, hipStream_t s, const Dev& D, const Prm& prm, int mode);
+hipError_t backward_mfma_replay_1(int code, dim3 grid, hipStream_t s, const Dev& D, int ddp);
+hipError_t backward_mfma_replay_3(dim3 grid, hipStream_t s, const Dev& D, int ddp);
 }  // namespace ktab
 }  // namespace fddp
 

@@ -743,7 +743,9 @@ class SolverFDDP:
     def _debug(self, on=True):
         check(lib().fddp_set_debug(self._ptr, 1 if on else 0))
 
-    # SolverDDP getters (ddp.hpp:60-271)
+    # SolverDDP getters (ddp.hpp:60-271). Vxx / Vx / Q* are the last backward pass's, readable at any
+    # time: the first read after a pass replays its sweep on the device into the stores
+    # (fddp_get_quantity); _debug(True) fills them at every pass instead.
     K = property(lambda s: s._quantity(_abi.Q_K, s.problem.T, s.problem.nu_max, s.problem.ndx, "rows"))
     k = property(lambda s: s._quantity(_abi.Q_KV, s.problem.T, s.problem.nu_max, None, "rows"))
     fs = property(lambda s: s._quantity(_abi.Q_FS, s.problem.T + 1, s.problem.ndx))
@@ -871,8 +873,8 @@ class SolverBoxFDDP(SolverFDDP):
 
     @property
     def Quu_inv(self):
-        """SolverBoxFDDP::get_Quu_inv (box-fddp.cpp:162); needs _debug(True)
-        before the backward pass (device-side store)."""
+        """SolverBoxFDDP::get_Quu_inv (box-fddp.cpp:162) of the last backward pass (the knots
+        whose gains came from the box QP; zero elsewhere)."""
         p = self.problem
         return self._quantity(_abi.Q_QUU_INV, p.T, p.nu_max, p.nu_max, "both")
 

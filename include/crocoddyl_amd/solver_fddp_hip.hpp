@@ -374,13 +374,19 @@ class SolverFDDP {
   const std::vector<double>& get_costs_try() const { return costs_try_; }
   const std::vector<int32_t>& get_step_status() const { return step_status_; }
   // SolverDDP getters (ddp.hpp:60-271), element 0: K_[t] (nu x ndx, column-major), k_[t],
-  // fs_[t]; Vxx / Vx / Q* need set_debug(true) before the backward pass (device stores)
+  // fs_[t]; Vxx / Vx / Q* (Qxu: ndx x nu, Quu: nu x nu, column-major at the leading dimensions ndx /
+  // nu_max) of the last backward pass, readable at any time as the reference's: the first read after
+  // a pass replays its sweep on the device into the stores (fddp_hip.h fddp_get_quantity);
+  // set_debug(true) fills them at every pass instead, the cheaper choice when every pass is read
   std::vector<VectorXd> get_K() const { return quantity(FDDP_Q_K, dims_.T, (size_t)dims_.nu_max * dims_.ndx); }
   std::vector<VectorXd> get_k() const { return quantity(FDDP_Q_KV, dims_.T, dims_.nu_max); }
   std::vector<VectorXd> get_fs() const { return quantity(FDDP_Q_FS, dims_.T + 1, dims_.ndx); }
   std::vector<VectorXd> get_Vxx() const { return quantity(FDDP_Q_VXX, dims_.T + 1, (size_t)dims_.ndx * dims_.ndx); }
   std::vector<VectorXd> get_Vx() const { return quantity(FDDP_Q_VX, dims_.T + 1, dims_.ndx); }
+  std::vector<VectorXd> get_Qxx() const { return quantity(FDDP_Q_QXX, dims_.T, (size_t)dims_.ndx * dims_.ndx); }
+  std::vector<VectorXd> get_Qxu() const { return quantity(FDDP_Q_QXU, dims_.T, (size_t)dims_.ndx * dims_.nu_max); }
   std::vector<VectorXd> get_Quu() const { return quantity(FDDP_Q_QUU, dims_.T, (size_t)dims_.nu_max * dims_.nu_max); }
+  std::vector<VectorXd> get_Qx() const { return quantity(FDDP_Q_QX, dims_.T, dims_.ndx); }
   std::vector<VectorXd> get_Qu() const { return quantity(FDDP_Q_QU, dims_.T, dims_.nu_max); }
   void set_debug(bool on) { check(fddp_set_debug(h_.get(), on ? 1 : 0), "fddp_set_debug"); }
   std::vector<VectorXd> get_xs_try() const {
@@ -583,6 +589,11 @@ class SolverBoxFDDP : public SolverFDDP {
     params_.th_stop = 5e-5;
     push();
   }
+  // SolverBoxFDDP::get_Quu_inv (box-fddp.cpp:162), element 0: nu x nu per knot, column-major at the
+  // leading dimension nu_max; zero on a knot whose gains did not come from the box QP
+  std::vector<VectorXd> get_Quu_inv() const {
+    return quantity(FDDP_Q_QUU_INV, dims_.T, (size_t)dims_.nu_max * dims_.nu_max);
+  }
 };
 
 // SolverDDP (ddp.hpp:46-306, ddp.cpp:39-310) on the GPU: the handle's solver kind
@@ -607,6 +618,11 @@ class SolverBoxDDP : public SolverDDP {
       : SolverDDP(problem, device, FDDP_SOLVER_BOXDDP) {
     params_.th_stop = 5e-5;
     push();
+  }
+  // SolverBoxFDDP::get_Quu_inv (box-fddp.cpp:162), element 0: nu x nu per knot, column-major at the
+  // leading dimension nu_max; zero on a knot whose gains did not come from the box QP
+  std::vector<VectorXd> get_Quu_inv() const {
+    return quantity(FDDP_Q_QUU_INV, dims_.T, (size_t)dims_.nu_max * dims_.nu_max);
   }
 };
 

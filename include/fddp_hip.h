@@ -421,7 +421,25 @@ int fddp_get_us_try(fddp_handle* h, double* out);
 #define FDDP_Q_FS 8   /* (T+1) x ndx (gaps) */
 #define FDDP_Q_K 9    /* T x nu_max*ndx (K_, nu x ndx col-major) */
 #define FDDP_Q_KV 10  /* T x nu_max (k_) */
-/* The following need fddp_set_debug(h, 1) before the backward pass. */
+/* The following are the last backward pass's (SolverDDP's Vxx_, Vx_, Q*_ members; ddp.hpp:191-221),
+ * readable at any time, as the reference's getters. The sweep does not store them (at the headline
+ * size they are about 16 GB): the library keeps them in stores of their own, and
+ *   - with fddp_set_debug(h, 1) every backward pass fills the stores, and a read copies them;
+ *   - else, if the stores hold the last pass's values (an earlier read, or a pass made in debug mode),
+ *     a read copies them: also between a calcDiff and the next backward pass, where the reference
+ *     returns the previous pass's values too;
+ *   - else, if everything the last pass read is still on the device, the first read allocates the
+ *     stores (once, zero-filled, the sizes below x B x 8 bytes, kept until fddp_destroy) and replays
+ *     that pass's sweep once into them: the same kernel plan on the same inputs, so the same bits as
+ *     debug mode gives. K, k and the solver state are not changed. Further reads of the same pass
+ *     copy;
+ *   - before any backward pass of the handle: zeros;
+ *   - otherwise FDDP_ERR_INVALID_ARG: the derivatives of the last backward pass have been
+ *     overwritten (a calcDiff, fddp_set_knots, fddp_set_control_limits, a change of solver kind or
+ *     fddp_mpc_shift came after it) and its values were not stored. fddp_set_debug(h, 1) keeps the
+ *     stores filled at every pass.
+ * Reads from inside an iteration callback of fddp_solve follow the same rules. An element whose
+ * last backward pass failed (backward_error) has the failing attempt's partial values: unspecified. */
 #define FDDP_Q_VXX 11 /* (T+1) x ndx*ndx */
 #define FDDP_Q_VX 12  /* (T+1) x ndx */
 #define FDDP_Q_QXX 13 /* T x ndx*ndx */
@@ -435,7 +453,9 @@ int fddp_get_us_try(fddp_handle* h, double* out);
 #define FDDP_Q_COST 19 /* (T+1) x 1: data[t].cost of the current candidate (after
                           fddp_problem_calc / calc_diff or a solve) */
 int fddp_get_quantity(fddp_handle* h, int which, double* out);
-/* Store Vxx/Vx/Q* per knot during backward passes (costs HBM traffic). */
+/* Store Vxx/Vx/Q* per knot during every backward pass (costs HBM traffic in the sweep; the
+ * cheaper choice for callers that read them after every pass: without it each first read
+ * replays the sweep, see above). */
 int fddp_set_debug(fddp_handle* h, int on);
 
 /* ---- control limits and the box-constrained solver ------------------------ */
